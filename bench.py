@@ -4,8 +4,17 @@ A "step" is one full pass of the hot path (fused sample + BVH trace + shade + re
 texir_irt_generate) over the workload's valid texels at its spp.  Inputs (BVH, radiance texture, texel
 G-buffers, shifts) are resident in HBM before the timed region.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c4|c4_scan|c2|c1|tiny]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c4|c4_scan|c2|c1|tiny] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline needs: it sets up the workload, runs W warm-up steps, times K steps and prints the line
+(`value` = Mrays/s over the K steps, `ms_per_step` = wall milliseconds of one timed step).  Everything else -- the CPU baseline, the roofline
+and its live fingerprint, the 2/4/8-rank projection, the material step, the sibling workloads, the stages end to end, the N > 1 assembly
+check -- runs with `--full` only, and only `--full` writes the full record.  `--mat`, `--e2e` and `--extra` select such side legs and need `--full`.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed: DIR/irradiance.npy, float32, the [res^2, 3] irradiance
+texture a caller of texir_irt_generate receives -- or, when that exceeds 64 MB (c4: 201 MB), the rows of DUMP_SAMPLE_ROWS of its valid texels
+drawn with a fixed seed, in ascending texel order.  The inputs are seeded, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under torch.distributed.run with N ranks
 (one per GPU, backend nccl = RCCL); it refuses loudly when the box has fewer than N devices.
@@ -14,7 +23,7 @@ Multi-GPU: one process per GPU; the compacted valid-texel list is dealt block-cy
 (strong scaling of ONE texture), each rank writes its texels into a zero-initialised full texture and a single
 RCCL all_gather of the ranks' compacted values assembles it (disjoint support: the same bits as an all_reduce(SUM) at a twelfth of the bytes) -- inside the timed region.
 
-Prints ONE compact JSON line (rank 0; <= 3 KB by construction, `compact_line`) and writes the whole record -- every limit with its numerator and denominator, the
+Prints ONE compact JSON line (rank 0; <= 3 KB by construction, `compact_line`) and, with --full, writes the whole record -- every limit with its numerator and denominator, the
 occupancy sweep, the per-shard projection, the sibling workloads, the stages end to end -- to gpurun_out/bench_full.json ($TEXIR_BENCH_FULL overrides; `"full"` in
 the line names it).  In the full record `roofline` carries the bounds that hold (all <= 1), each = a per-launch counter of the
 dominant kernel (rocprofv3 --pmc, committed under profiles/pmc_<workload>.json together with a hash of the kernel sources
@@ -648,6 +657,24 @@ def write_full(full):
     return os.path.relpath(path, ROOT) if os.path.abspath(path).startswith(ROOT + os.sep) else path
 
 
+DUMP_CAP_BYTES = 64 << 20         # --dump-outputs writes at most this much
+DUMP_SAMPLE_ROWS = 1 << 21        # valid texels kept when the whole texture exceeds the cap (24 MB of float32 rows)
+DUMP_SEED = 666
+
+
+def dump_outputs(out_dir, irr, valid):
+    """--dump-outputs: the irradiance texture of the last timed step ([res^2, 3] float32, what texir_irt_generate hands its caller) as
+    out_dir/irradiance.npy -- whole when it fits DUMP_CAP_BYTES, else a seeded sample of its valid texels' rows in ascending texel order"""
+    os.makedirs(out_dir, exist_ok=True)
+    if irr.numel() * 4 > DUMP_CAP_BYTES:
+        rows = np.flatnonzero(valid.reshape(-1) > 0)
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=min(DUMP_SAMPLE_ROWS, rows.size), replace=False))
+        irr = irr[torch.from_numpy(pick).to(irr.device)]
+    a = irr.detach().to(torch.float32).cpu().numpy()
+    assert a.nbytes <= DUMP_CAP_BYTES, a.nbytes
+    np.save(os.path.join(out_dir, "irradiance.npy"), a)
+
+
 XGMI_LINK_GBS = 153.0         # per xGMI link and direction (SURVEY.md section 5: 7 links x ~153 GB/s per GPU, point to point)
 
 
@@ -731,13 +758,21 @@ def main():
     ap.add_argument("--mat-cube", type=int, default=128)
     ap.add_argument("--no-project", dest="project", action="store_false", help="skip the per-shard timing of the 2/4/8-rank partitions (N = 1 only; `ranks.projected`)")
     ap.add_argument("--e2e", dest="e2e", action="store_true", default=None, help="time the stages end to end from files on disk (tools/stage_time.py): `e2e` in the line; "
-                    "default: on with the full c4 headline line, off otherwise")
+                    "default: on with --full on c4, off otherwise")
     ap.add_argument("--no-e2e", dest="e2e", action="store_false")
     ap.add_argument("--extra", default=None, help="comma-separated extra workloads timed after the headline (IrT only), reported under extra_workloads; "
-                    "default: c4_scan (the hostile sibling) and house (the multi-room family) next to the full c4 headline line, nothing otherwise or with --no-cpu / --no-mat; `none` switches it off")
+                    "default: c4_scan (the hostile sibling) and house (the multi-room family) with --full on c4, nothing otherwise or with --no-cpu / --no-mat; `none` switches it off")
+    ap.add_argument("--full", action="store_true", help="run every side measurement too (CPU baseline, roofline, projection, material step, sibling workloads, "
+                    "stages end to end, N > 1 assembly check) and write the full record; off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's irradiance texture (or a seeded "
+                    "sample of it, <= 64 MB) to DIR/irradiance.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.mat or args.e2e or (args.extra or "none") != "none"):
+        ap.error("--mat, --e2e and --extra select side measurements: they need --full")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn(args)
 
@@ -830,6 +865,7 @@ def main():
             tt = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if world > 1 and args.full:
             # per-rank kernel time (load imbalance of the block-cyclic shards shows here) and a check of the assembly: rank 0 re-traces a 1 %
             # sample of the texel blocks -- its own and the other ranks' -- alone and compares with the all-reduced texture, bit for bit
             km = [torch.zeros(1, device=dev, dtype=torch.float64) for _ in range(world)]
@@ -856,8 +892,8 @@ def main():
                      "assembled_ok": ok, "assembled_check": "rank 0 alone re-traced every 100th %d-texel block of the list; bit-equal to the assembled (all-gathered) texture" % BLOCK}
         T, _, tex_res, _, style = WORKLOADS[name]
         n_valid = int(ids_all.numel())
-        fp = irt_fingerprint(sc, d_pos, d_nrm, d_shift, ids_all, spp, dev) if world == 1 else None
-        if world == 1 and args.project:
+        fp = irt_fingerprint(sc, d_pos, d_nrm, d_shift, ids_all, spp, dev) if world == 1 and args.full else None
+        if world == 1 and args.full and args.project:
             ranks = {"projected": project_scaling(sc, d_pos, d_nrm, d_shift, ids_all, spp, res, dev, kern_ms)}
         return {"sc": sc, "sc0": sc0, "pos": pos, "nrm": nrm, "valid": valid, "shift": shift, "res": res, "spp": spp, "irr": irr, "ids": ids,
                 "dt": dt, "kern_ms": kern_ms, "ranks": ranks, "n_valid": n_valid, "build_s": build_s, "make_s": t_make, "fingerprint": fp, "kernel": sc.irt_kernel_name(int(ids.numel()), spp),
@@ -868,8 +904,10 @@ def main():
                                sc.texture_layout(), "RGB32F tiles, layout %d" % sc.texture_layout()))}
 
     r = run_irt(args.workload, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["irr"], r["valid"])
     mat = mat_view = None
-    if not args.no_mat and (args.workload == "c4" or args.mat):
+    if args.full and not args.no_mat and (args.workload == "c4" or args.mat):
         import contextlib
         with contextlib.redirect_stdout(sys.stderr):          # (constructors print like the reference's; stdout carries the JSON line only)
             if world > 1:
@@ -902,29 +940,30 @@ def main():
             out["ranks"] = r["ranks"]
             if "assembled_ok" in r["ranks"]:
                 out["assembled_ok"] = r["ranks"]["assembled_ok"]
-        rays_this_rank = int(r["ids"].numel()) * r["spp"]
-        alg = cpu = None
-        if not args.no_cpu:
-            cpu, counters = cpu_leg(r["sc0"], r["pos"], r["nrm"], r["valid"], r["shift"], r["spp"], timed=world == 1)
-            alg = algorithmic_bytes_per_ray(counters, r["spp"])
-        out["roofline"] = roofline(args.workload, r["kernel"], r["kern_ms"], rays_this_rank, world, alg, r["fingerprint"])
-        # what one launch MUST move through HBM at least once: the scene it reads (tree in both forms, triangles, corner uvs, the hit shader's texture copy),
-        # the texel G-buffers + id list, and the texture it writes -- everything beyond this in `traffic` is re-reading (cache misses), everything in
-        # `algorithmic` beyond `traffic` was served by L1 / L2 / LDS / the scalar cache
-        info = r["sc"].info()
-        comp = (info["node_bytes"] + info["tri_bytes"] + info["uv_bytes"] + info["tex_bytes"]
-                + int(r["ids"].numel()) * (12 + 12 + 8 + 4) + int(r["ids"].numel()) * 12)
-        out["roofline"]["compulsory_bytes"] = int(comp)
-        out["roofline"]["reading"] = ("top-level achieved / peak / frac / traffic = the FABRIC side of L2 (requests to the Infinity Cache and HBM together: Infinity-Cache hits are "
-                                      "included, so HBM proper carries less) -- measured, and NOT what bounds this kernel: see `binding` and `waves` (a dependent fetch -> box test -> sort "
-                                      "-> push chain at 8 waves per SIMD); compulsory_bytes / traffic = %.4f of the fabric traffic is first-touch, the rest is re-read"
-                                      % (comp / out["roofline"]["traffic"] if out["roofline"].get("traffic") else float("nan")))
-        if cpu is not None:
-            out["cpu_baseline"] = cpu
+        if args.full:
+            rays_this_rank = int(r["ids"].numel()) * r["spp"]
+            alg = cpu = None
+            if not args.no_cpu:
+                cpu, counters = cpu_leg(r["sc0"], r["pos"], r["nrm"], r["valid"], r["shift"], r["spp"], timed=world == 1)
+                alg = algorithmic_bytes_per_ray(counters, r["spp"])
+            out["roofline"] = roofline(args.workload, r["kernel"], r["kern_ms"], rays_this_rank, world, alg, r["fingerprint"])
+            # what one launch MUST move through HBM at least once: the scene it reads (tree in both forms, triangles, corner uvs, the hit shader's texture copy),
+            # the texel G-buffers + id list, and the texture it writes -- everything beyond this in `traffic` is re-reading (cache misses), everything in
+            # `algorithmic` beyond `traffic` was served by L1 / L2 / LDS / the scalar cache
+            info = r["sc"].info()
+            comp = (info["node_bytes"] + info["tri_bytes"] + info["uv_bytes"] + info["tex_bytes"]
+                    + int(r["ids"].numel()) * (12 + 12 + 8 + 4) + int(r["ids"].numel()) * 12)
+            out["roofline"]["compulsory_bytes"] = int(comp)
+            out["roofline"]["reading"] = ("top-level achieved / peak / frac / traffic = the FABRIC side of L2 (requests to the Infinity Cache and HBM together: Infinity-Cache hits are "
+                                          "included, so HBM proper carries less) -- measured, and NOT what bounds this kernel: see `binding` and `waves` (a dependent fetch -> box test -> sort "
+                                          "-> push chain at 8 waves per SIMD); compulsory_bytes / traffic = %.4f of the fabric traffic is first-touch, the rest is re-read"
+                                          % (comp / out["roofline"]["traffic"] if out["roofline"].get("traffic") else float("nan")))
+            if cpu is not None:
+                out["cpu_baseline"] = cpu
     # further workloads (IrT only), never the headline
-    if args.extra is None:          # the full default line (what the driver runs) carries the hostile sibling; tool invocations (--no-cpu / --no-mat) stay lean
+    if args.extra is None:          # the --full line on c4 carries the hostile sibling; tool invocations (--no-cpu / --no-mat) stay lean
         # (N > 1 stays lean: every extra workload costs rank 0 another ~25 s of generation + cache hand-off inside the driver's wall clock, and the siblings are never the headline)
-        args.extra = "c4_scan,house" if (args.workload == "c4" and not args.no_cpu and not args.no_mat and world == 1) else ""
+        args.extra = "c4_scan,house" if (args.full and args.workload == "c4" and not args.no_cpu and not args.no_mat and world == 1) else ""
     extras = [w for w in args.extra.split(",") if w and w != "none"]
     if extras:
         del r
@@ -944,9 +983,9 @@ def main():
             torch.cuda.empty_cache()
         if rank == 0:
             out["extra_workloads"] = ex
-    # the stages end to end, files on disk to files on disk (tools/stage_time.py): default with the full headline line, --e2e / --no-e2e force it
+    # the stages end to end, files on disk to files on disk (tools/stage_time.py): default with --full on c4, --e2e / --no-e2e force it
     if args.e2e is None:
-        args.e2e = args.workload == "c4" and not args.no_cpu and not args.no_mat and world == 1
+        args.e2e = args.full and args.workload == "c4" and not args.no_cpu and not args.no_mat and world == 1
     if args.e2e and rank == 0 and world == 1:
         r = None
         torch.cuda.empty_cache()
@@ -959,7 +998,7 @@ def main():
         except Exception as e:                # the headline line must survive a failing stage run; the failure is in the line
             out["e2e"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
     if rank == 0:
-        path = write_full(out)
+        path = write_full(out) if args.full else None          # a plain run's line is its whole record
         print(compact_line(out, path), flush=True)
     if world > 1:
         dist.barrier()

@@ -195,6 +195,36 @@ def test_compact_line_fits_the_drivers_capture_and_keeps_the_contract_keys():
     assert len(bench.compact_line(full3, "x.json")) <= bench.LINE_CAP
 
 
+def test_dump_outputs_writes_the_whole_texture_or_a_seeded_sample_under_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    res = 64
+    irr = torch.arange(res * res * 3, dtype=torch.float32).reshape(-1, 3)
+    valid = (np.arange(res * res) % 3 != 0).astype(np.uint8).reshape(res, res)
+    bench.dump_outputs(str(tmp_path / "whole"), irr, valid)
+    a = np.load(tmp_path / "whole" / "irradiance.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, irr.numpy())
+    # over the cap: a fixed, seeded sample of the valid texels' rows in ascending order, the same on every call
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 4096)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ROWS", 100)
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), irr, valid)
+    b, c = np.load(tmp_path / "s1" / "irradiance.npy"), np.load(tmp_path / "s2" / "irradiance.npy")
+    assert b.dtype == np.float32 and b.shape == (100, 3) and b.nbytes <= 4096 and np.array_equal(b, c)
+    rows = (b[:, 0] / 3).astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.all(valid.reshape(-1)[rows] > 0) and np.array_equal(b, irr.numpy()[rows])
+
+
+def test_side_legs_need_full_and_steps_are_counted():
+    """--mat / --e2e / --extra select side measurements, which only --full runs: asking for one without it is an error, not a silent no-op"""
+    import subprocess
+    for extra in (["--mat"], ["--e2e"], ["--extra", "c4_scan"], ["--steps", "0"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and '"metric"' not in r.stdout, (extra, r.returncode, r.stderr[-500:])
+        assert ("need --full" if extra[0] != "--steps" else "--steps must be >= 1") in r.stderr, (extra, r.stderr[-500:])
+
+
 def test_write_full_record_goes_to_the_named_file(tmp_path, monkeypatch):
     import bench
     p = tmp_path / "sub" / "full.json"

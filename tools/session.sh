@@ -11,7 +11,7 @@ export TEXIR_SYNTH_CACHE=${TEXIR_SYNTH_CACHE:-/tmp/texir_synth}
 cd $R
 irt_line() {  # workload, extra env... -> "value ms_per_step kernel_ms"
   wl=$1; shift
-  env "$@" timeout 600 python bench.py --workload $wl --steps 2 --warmup 1 --no-cpu --no-mat --extra none --no-project 2>/dev/null | tail -1 | \
+  env "$@" timeout 600 python bench.py --workload $wl --steps 2 --warmup 1 --full --no-cpu --no-mat --extra none --no-project 2>/dev/null | tail -1 | \
     python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])" 2>&1 | tail -1
 }
 for step in "$@"; do
@@ -19,11 +19,11 @@ for step in "$@"; do
   case $step in
     tests)    timeout 3000 python -m pytest tests -m gpu -q > $out/pytest.txt 2>&1; echo "pytest rc $?" >> $out/pytest.txt; tail -4 $out/pytest.txt ;;
     tests-x)  timeout 3000 python -m pytest tests -m gpu -x -q > $out/pytest.txt 2>&1; echo "pytest rc $?" >> $out/pytest.txt; tail -4 $out/pytest.txt ;;
-    bench)    TEXIR_BENCH_FULL=$out/bench_full.json timeout 1800 python bench.py --steps 5 --warmup 1 > $out/bench.json 2> $out/bench.err; echo "bench rc $?"; tail -c 600 $out/bench.err ;;
+    bench)    TEXIR_BENCH_FULL=$out/bench_full.json timeout 1800 python bench.py --steps 5 --warmup 1 --full > $out/bench.json 2> $out/bench.err; echo "bench rc $?"; tail -c 600 $out/bench.err ;;
     driver)   TEXIR_BENCH_FULL=$out/bench_driver_full.json timeout 1800 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver.json 2> $out/bench_driver.err; echo "driver-shaped bench rc $?"; tail -c 3200 $out/bench_driver.json ;;
-    bench-lean) TEXIR_BENCH_FULL=$out/bench_lean_full.json timeout 900 python bench.py --steps 2 --warmup 1 --no-e2e --extra none > $out/bench_lean.json 2> $out/bench_lean.err; echo "bench rc $?" ;;
+    bench-lean) TEXIR_BENCH_FULL=$out/bench_lean_full.json timeout 900 python bench.py --steps 2 --warmup 1 --full --no-e2e --extra none > $out/bench_lean.json 2> $out/bench_lean.err; echo "bench rc $?" ;;
     gloo2)    TEXIR_BENCH_FULL=$out/gloo2_full.json TEXIR_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 \
-                --workload tiny --steps 1 --warmup 1 --no-cpu --mat --mat-steps 4 --mat-res 512 --mat-cube 32 > $out/gloo2.json 2> $out/gloo2.err; echo "rc $?"
+                --workload tiny --steps 1 --warmup 1 --full --no-cpu --mat --mat-steps 4 --mat-res 512 --mat-cube 32 > $out/gloo2.json 2> $out/gloo2.err; echo "rc $?"
               python - $out/gloo2.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1].replace(".json", "_full.json")))
