@@ -352,8 +352,8 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
         idy = __builtin_amdgcn_rcpf(fabsf(dy) > ooeps ? dy : copysignf(ooeps, dy));
         idz = __builtin_amdgcn_rcpf(fabsf(dz) > ooeps ? dz : copysignf(ooeps, dz));
         oodx = ox * idx; oody = oy * idy; oodz = oz * idz;
-        // byte offsets of the NEAR plane array of each axis inside a 128-byte float node (far = offset ^ 16), wave-uniform when the rays' signs agree
-        lon = (idx < 0.f ? 16u : 0u) | ((idy < 0.f ? 48u : 32u) << 8) | ((idz < 0.f ? 80u : 64u) << 16);
+        // the ray's octant (bit a: negative direction along axis a), wave-uniform when the rays' signs agree: it names the body of a wave-uniform node step
+        lon = (idx < 0.f ? 1u : 0u) | (idy < 0.f ? 2u : 0u) | (idz < 0.f ? 4u : 0u);
 #if TEXIR_TRI_WATERTIGHT
         const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
         kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
@@ -369,7 +369,7 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
 #endif
     }
     // what the lanes of the wave agree on (decided per ray batch; a streamed wave decides again after every refill, over the lanes that hold a ray)
-    uint32_t son; bool signs_uniform; uint32_t son0, son1, son2;
+    uint32_t son; bool signs_uniform;
 #if TEXIR_TRI_WATERTIGHT
     int kz0; [[maybe_unused]] bool kz_uniform;
 #endif
@@ -392,7 +392,6 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             kz_uniform = !__any(kz != kz0);
 #endif
         }
-        son0 = son & 255u; son1 = (son >> 8) & 255u; son2 = son >> 16;
     };
     agree(true);
     Hit h;
@@ -459,26 +458,49 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
         // together: 45 % of the wave-level node steps on c4): a vector fetch costs the L1 64 lanes x 64 bytes whether or not the lanes
         // agree (tools/tcp_node.hip: 60 clocks per wave fetch from 1 to 16 distinct nodes); the scalar path costs it nothing.  When the
         // wave's rays also share their direction signs (a pass is one ~2.5 degree direction cell: they do unless the cell straddles an
-        // axis plane), the step reads the FLOAT planes of the node (GpuNode4F) through wave-uniform offsets that pick the near / far
-        // plane arrays: no byte -> float conversion (24 per step), no sign select, no origin / cell-size set-up.
+        // axis plane), the step reads the FLOAT planes of the node (GpuNode4F) through the scalar cache: no byte -> float conversion
+        // (24 per step), no sign select, no origin / cell-size set-up.
+        //   The node is fetched by three loads at fixed offsets from ONE base address: the x and y plane arrays (64 B, s_load_dwordx16), the z plane
+        // arrays (32 B, x8) and the child codes (16 B, x4).  Which array of an axis is the near one is the octant's business, and the octant is the
+        // wave's (`son`): one body per octant picks its planes at compile time, and the branch to it runs while the loads are in flight.  (Round 2-6
+        // form: six 16-byte loads through per-axis near / far offsets plus one for the codes -- each a 64-bit address sum of its own, the offsets
+        // parked in VGPR lanes under the kernel's SGPR pressure and read back by v_readlane, all on the step's dependent chain.)
         const int n0 = __builtin_amdgcn_readfirstlane(node);
 #if TEXIR_CHAIN_PROBE
         probe_scalar_path = signs_uniform && !__any(node != n0);
 #endif
         if (signs_uniform && !__any(node != n0)) {
-            typedef float F4 __attribute__((ext_vector_type(4)));
+            typedef float F16 __attribute__((ext_vector_type(16)));
+            typedef float F8 __attribute__((ext_vector_type(8)));
             typedef int32_t I4 __attribute__((ext_vector_type(4)));
             const char __attribute__((address_space(4)))* const nb =
                 (const char __attribute__((address_space(4)))*)(reinterpret_cast<const char*>(sc.nodes4f) + ((uint32_t)n0 << 7));
-            auto ldf = [&](uint32_t off) { return *(const F4 __attribute__((address_space(4)))*)(nb + off); };
-            const F4 pnx = ldf(son0), pfx = ldf(son0 ^ 16u), pny = ldf(son1), pfy = ldf(son1 ^ 16u), pnz = ldf(son2), pfz = ldf(son2 ^ 16u);
+            const F16 pxy = *(const F16 __attribute__((address_space(4)))*)nb;           // lo.x, hi.x, lo.y, hi.y
+            const F8 pz = *(const F8 __attribute__((address_space(4)))*)(nb + 64u);      // lo.z, hi.z
             const I4 ch = *(const I4 __attribute__((address_space(4)))*)(nb + 96u);
+            auto body = [&](auto OCT) __attribute__((always_inline)) {
+                constexpr int o = decltype(OCT)::value;
+                constexpr int nx = (o & 1) ? 4 : 0, ny = (o & 2) ? 12 : 8, nz = (o & 4) ? 4 : 0;       // near arrays; the far one is the other of the pair (^ 4)
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float nxt = pnx[k] * idx - oodx, fxt = pfx[k] * idx - oodx, nyt = pny[k] * idy - oody, fyt = pfy[k] * idy - oody;
-                const float nzt = pnz[k] * idz - oodz, fzt = pfz[k] * idz - oodz;
-                const float tn = fmaxf(fmaxf(nxt, nyt), fmaxf(nzt, 0.f)), tf = fminf(fminf(fxt, fyt), fminf(fzt, h.t));
-                key[k] = tn <= tf ? tn : __builtin_inff();
+                for (int k = 0; k < 4; k++) {
+                    const float nxt = pxy[nx + k] * idx - oodx, fxt = pxy[(nx ^ 4) + k] * idx - oodx;
+                    const float nyt = pxy[ny + k] * idy - oody, fyt = pxy[(ny ^ 4) + k] * idy - oody;
+                    const float nzt = pz[nz + k] * idz - oodz, fzt = pz[(nz ^ 4) + k] * idz - oodz;
+                    const float tn = fmaxf(fmaxf(nxt, nyt), fmaxf(nzt, 0.f)), tf = fminf(fminf(fxt, fyt), fminf(fzt, h.t));
+                    key[k] = tn <= tf ? tn : __builtin_inff();
+                }
+            };
+            // (each case ends in a distinct empty asm statement: without it the compiler merges the eight bodies back into one that indexes the loaded
+            // planes by run-time octant -- index moves, spills -- undoing the specialisation)
+            switch (son) {
+                case 0: body(std::integral_constant<int, 0>{}); asm volatile("; octant 0"); break;
+                case 1: body(std::integral_constant<int, 1>{}); asm volatile("; octant 1"); break;
+                case 2: body(std::integral_constant<int, 2>{}); asm volatile("; octant 2"); break;
+                case 3: body(std::integral_constant<int, 3>{}); asm volatile("; octant 3"); break;
+                case 4: body(std::integral_constant<int, 4>{}); asm volatile("; octant 4"); break;
+                case 5: body(std::integral_constant<int, 5>{}); asm volatile("; octant 5"); break;
+                case 6: body(std::integral_constant<int, 6>{}); asm volatile("; octant 6"); break;
+                default: body(std::integral_constant<int, 7>{}); asm volatile("; octant 7"); break;
             }
             code[0] = ch.x; code[1] = ch.y; code[2] = ch.z; code[3] = ch.w;
         } else {
