@@ -11,6 +11,7 @@ Fixtures (SURVEY.md 8c pins):
   irt_box.npz      models/tracer_o3d_irt.py:145-180 whole forward() loop, 12-tri box, 32^2 texels, N=64
   irt_room.npz     same, 20k-tri room, 64^2 texels, N=256   (cast_rays answered by the f64 brute-force tracer)
   render_loss.npz  models/loss.py:81-115,214-295 RenderLoss stages 0/1/2, values + grads
+  render_loss_edges.npz  the same on a 6x32x32 view whose classes sit at the edges of the stage-1 quantile (ties, n = 1/2/6, n > 1024, class 43)
   cube2pano.npz    utils/Cube2Pano.py:119-144 ToPano
   mat_trajectory.npz  trainer/train_material.py:245-356,408-605 the trainer loop itself (3 steps per stage) on a pixel-parameter model
   pano2cube.npz    utils/Pano2Cube.py:24-102 grids + Tocube (nearest and bilinear); cv2.Rodrigues answered by scipy
@@ -320,6 +321,84 @@ def render_loss():
     save("render_loss.npz", **out)
 
 
+def render_loss_edges():
+    """models/loss.py:81-115,214-295 on one 6x32x32 view whose classes sit at the stage-1 quantile's edges (ids stored as uint8; 255 = none):
+    c0 1300 highlight pixels (> one 1024-thread select block); c1 all highlight values tied, and every non-highlight roughness equal to them
+    (L1 sign(0)); c2 a tie run straddling rank k0 = floor(0.4 (n-1)); c3 a tie run ending at k0; c4/c5/c6 n = 1/2/6 (0.4*5 = 2 exact);
+    c7 empty; c8 pixels without highlight; c9 values 0.5 + i ulp (differ in the lowest key byte); c43 with highlights (tau forced to 0.8).
+    Layout b (hl_id_b) drops c43's highlights (tau 0); it changes stage 1 only, the one stage that reads the highlight mask."""
+    torch.manual_seed(22)
+    rng = np.random.default_rng(22)
+    C, F, h, w, R = 49, 6, 32, 32, 3
+    P = F * h * w
+    # (class, pixels, highlight pixels) of the special classes; the rest of the view is classes 10..48 at random
+    spec = [(0, 1700, 1300), (1, 400, 300), (2, 200, 100), (3, 200, 100), (4, 50, 1), (5, 50, 2), (6, 50, 6), (8, 300, 0), (9, 50, 11),
+            (43, 150, 60), (255, 200, 0)]
+    seg = np.full(P, 255, np.int64)
+    hl = np.zeros(P, bool)
+    rest = [c for c in range(10, C) if c != 43]
+    at = 0
+    for c, n, k in spec:
+        seg[at:at + n] = c
+        hl[at:at + k] = True
+        at += n
+    seg[at:] = rng.choice(rest, P - at)
+    hl[at:] = rng.random(P - at) < 0.3
+    # the first 2048 pixels keep contiguous class runs, the rest is shuffled (waves mixing many classes)
+    perm = np.concatenate([np.arange(2048), 2048 + rng.permutation(P - 2048)])
+    seg, hl = seg[perm], hl[perm]
+    hl &= seg != 255
+    room = rng.integers(0, R, P)
+    room[rng.permutation(P)[:300]] = 255
+    gt = torch.exp(torch.randn(P, 3))
+    gt_mask = (torch.rand(P, 1) > 0.1).float()
+    empty = (torch.rand(P, 1) > 0.1).float()
+    rgb0 = torch.exp(torch.randn(P, 3) * 0.5)
+    alb0 = torch.rand(P, 3)
+    r0 = torch.rand(P, 1) * 0.79 + 0.01
+    rw0 = torch.rand(P, 1) * 0.79 + 0.01
+
+    def put(c, vals):
+        idx = np.flatnonzero((seg == c) & hl)
+        assert idx.size == len(vals), (c, idx.size, len(vals))
+        rw0[idx, 0] = torch.from_numpy(rng.permutation(np.asarray(vals, np.float32)))
+
+    put(1, np.full(300, 0.3))
+    r0[np.flatnonzero(seg == 1), 0] = torch.tensor(0.3)
+    put(2, np.concatenate([0.1 + 0.001 * np.arange(30), np.full(20, 0.2), 0.3 + 0.001 * np.arange(50)]))     # k0 = 39, k1 = 40: inside the run
+    put(3, np.concatenate([0.1 + 0.001 * np.arange(30), np.full(10, 0.2), 0.25 + 0.001 * np.arange(60)]))    # the run ends at k0 = 39
+    put(9, np.float32(0.5) + np.arange(11) * np.spacing(np.float32(0.5)))
+    onehot = lambda ids, n: torch.from_numpy((np.arange(n).reshape(n, 1) == ids[None]).astype(np.float32)).reshape(n, F, h, w, 1)
+    seg_mask = onehot(seg, C)
+    room_mask = onehot(room, R)
+    v = lambda t, k: t.reshape(F, h, w, k)
+    out = dict(seg_id=seg.astype(np.uint8), hl_id=hl.astype(np.uint8), room_id=room.astype(np.uint8), C=C, R=R, shape=np.array([F, h, w]),
+               gt=v(gt, 3).numpy(), gt_mask=v(gt_mask, 1).numpy(), empty_mask=v(empty, 1).numpy(), rgb=v(rgb0, 3).numpy(), albedo=v(alb0, 3).numpy(),
+               roughness=v(r0, 1).numpy(), roughness_womipmap=v(rw0, 1).numpy())
+    hl_b = hl & (seg != 43)
+    out["hl_id_b"] = hl_b.astype(np.uint8)
+    for lay, hh in (("a", hl), ("b", hl_b)):
+        fm = seg_mask * torch.from_numpy(hh.astype(np.float32)).reshape(1, F, h, w, 1)
+        for loss_type in ["L1", "L2"]:
+            L = ref_loss.RenderLoss(loss_type=loss_type, w_gradient=1)
+            for stage in ((0, 1, 2) if lay == "a" else (1,)):
+                rgb, alb, r, rw = (v(x, x.shape[1]).clone().requires_grad_(True) for x in (rgb0, alb0, r0, rw0))
+                preds = {"rgb": rgb, "albedo": alb, "roughness": r, "roughness_womipmap": rw, "empty_mask": v(empty, 1)}
+                res = L(v(gt, 3), preds, v(gt_mask, 1), fm, seg_mask, stage, room_mask)
+                res[0].backward()
+                assert rw.grad is None or not rw.grad.any()
+                assert (alb.grad is None or not alb.grad.any()) if stage else (r.grad is None or not r.grad.any())
+                k = "%s_%s_s%d_" % (lay, loss_type, stage)
+                out[k + "loss"] = res[0].detach().numpy()
+                out[k + "seg"] = np.float32(res[1])
+                out[k + "d_rgb"] = rgb.grad.numpy()
+                if stage == 0:
+                    out[k + "d_albedo"] = alb.grad.numpy()
+                else:
+                    out[k + "d_roughness"] = r.grad.numpy()
+    save("render_loss_edges.npz", **out)
+
+
 def cube2pano():
     torch.manual_seed(5)
     c2p = ref_c2p.Cube2Pano(pano_width=64, pano_height=32, cube_lenth=16, cube_channel=6, is_cuda=False)
@@ -494,6 +573,6 @@ def nirf():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["gen_dir", "spec_render", "query_irf", "irt_box", "irt_room", "render_loss", "cube2pano", "mat_trajectory", "pano2cube", "nirf", "diffuse", "test_render"]
+    which = sys.argv[1:] or ["gen_dir", "spec_render", "query_irf", "irt_box", "irt_room", "render_loss", "render_loss_edges", "cube2pano", "mat_trajectory", "pano2cube", "nirf", "diffuse", "test_render"]
     for w in which:
         globals()[w]()

@@ -4,6 +4,8 @@ Same constructor and forward signature/return tuple as the reference class; the 
 kernels behind texir_loss_forward.  The reference's [C,6,h,w,1] one-hot mask tensors are accepted as-is and
 compacted (once per mask tensor, cached) to 1-byte class / highlight / room ids.
 """
+import weakref
+
 import torch
 from torch import nn
 
@@ -106,16 +108,23 @@ class RenderLoss(nn.Module):
         self._cache = {}
 
     def _compact(self, seg_mask, floor_max_mask, room_seg_mask, dev):
-        key = tuple((t.data_ptr(), tuple(t.shape), t._version) if t is not None else None for t in (seg_mask, floor_max_mask, room_seg_mask))
+        # keyed by address, shape and version, and valid only while the SAME tensor objects are alive: a mask freed and replaced by a new one
+        # of the same shape can sit at the same address with the same _version.  The entry holds weak references only (a mask of a training
+        # view is ~19 MB; the cache must not keep it alive).
+        masks = (seg_mask, floor_max_mask, room_seg_mask)
+        key = tuple((t.data_ptr(), tuple(t.shape), t._version) if t is not None else None for t in masks)
         hit = self._cache.get(key)
-        if hit is None:
-            if len(self._cache) > 256:
-                self._cache.clear()
-            seg_id, hl, room_id, C, R = compact_masks(seg_mask, floor_max_mask, room_seg_mask)
-            mv = lambda t: None if t is None else t.to(dev).contiguous()
-            hit = (mv(seg_id), mv(hl), mv(room_id), C, R)
-            self._cache[key] = hit
-        return hit
+        if hit is not None and all((r is None) if t is None else (r() is t) for r, t in zip(hit[0], masks)):
+            return hit[1]
+        alive = lambda refs: all(r is None or r() is not None for r in refs)
+        self._cache = {k: v for k, v in self._cache.items() if alive(v[0])}
+        if len(self._cache) > 256:
+            self._cache.clear()
+        seg_id, hl, room_id, C, R = compact_masks(seg_mask, floor_max_mask, room_seg_mask)
+        mv = lambda t: None if t is None else t.to(dev).contiguous()
+        ids = (mv(seg_id), mv(hl), mv(room_id), C, R)
+        self._cache[key] = (tuple(None if t is None else weakref.ref(t) for t in masks), ids)
+        return ids
 
     def forward(self, gt_img, preds, gt_mask, floor_max_mask, seg_mask, stage=0, room_seg_mask=None):
         if stage not in (0, 1, 2):
