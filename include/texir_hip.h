@@ -356,6 +356,37 @@ typedef struct texir_adam_tex_job {
 TEXIR_API int texir_grad_add_masked(float* g /*dev*/, const float* g0 /*dev*/, const uint32_t* mask /*dev*/, int64_t n_texels, int32_t C, void* stream);
 TEXIR_API int texir_adam_step_tex_dev_batch(const texir_adam_tex_job* jobs /*host*/, int32_t n_jobs, void* stream);
 
+/* ---- the asset step between the two stages: replaces tools/padding_texture.py:49-87 (the script that turns the IrT stage's 0_irr_texture.hdr into the
+ * Mat stage's irt.hdr: scipy's Euclidean distance transform + grid_sample on the CPU, then the external Open Image Denoise binary) by launches on the
+ * device texture.  Nothing below allocates or synchronises: scratch is the caller's, so every launch can be recorded into a hipGraph.
+ *
+ * texir_texture_pad: img [H,W,C] f32, C in 1..4, H and W <= 16384.  A texel is a HOLE when the float32 sum of its channels in channel order
+ * (c0 + c1 + c2 ...) equals 0.0 -- the reference's rule (:54-56); (1, -1, 0) is a hole.
+ *   src [H*W] i32 (nullable output): src[t] = t for a non-hole; for a hole the flat index of a non-hole texel at minimal Euclidean distance, compared
+ *     as exact integer squared distances, whatever that distance is (no search window); -1 everywhere when the image has no non-hole texel.
+ *     TIE RULE (deterministic; independent of launch configuration and run): with the hole at (y, x), the candidate of a column is that column's non-hole
+ *     row nearest to y, the UPPER one of two equidistant rows; columns are visited in the order x, x-1, x+1, x-2, x+2, ... and the first candidate at the
+ *     minimal squared distance wins.
+ *   out [H,W,C] (!= img): non-holes keep their bits; a hole takes img[src[t]] (mode `nearest`: row_map == col_map == NULL) or, with (r, c) the texel
+ *     src[t] names, img[row_map[r], col_map[c]] and 0 where a map entry is -1 (mode `reference`: row_map [H], col_map [W] i32 tables of what
+ *     F.grid_sample(mode='nearest', align_corners=False) really reads for source index i -- rint(i - 0.5) in float32, half to even, i.e. one texel too low
+ *     for every odd i; texpost.reference_index_map builds them).  With src == -1 (no non-hole texel) out is a copy of img.
+ *   workspace: texir_texture_pad_workspace_bytes(H, W) bytes of device scratch. */
+TEXIR_API int64_t texir_texture_pad_workspace_bytes(int32_t H, int32_t W);
+TEXIR_API int texir_texture_pad(const float* img /*dev*/, int32_t H, int32_t W, int32_t C, const int32_t* row_map /*dev [H], nullable*/,
+                       const int32_t* col_map /*dev [W], nullable*/, float* out /*dev [H,W,C], != img*/, int32_t* src /*dev [H*W], nullable*/,
+                       void* workspace /*dev*/, void* stream);
+/* Stand-in for the Open Image Denoise call (:86-87; NOT a re-implementation of its network): an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010)
+ * on log(1 + max(x, 0)).  `iterations` (1..6) passes of the 5x5 B3-spline kernel [1 4 6 4 1]/16 x [1 4 6 4 1]/16 with hole size 2^it in pass it; the weight of
+ * tap q at texel p is k[dy] k[dx] exp(-E) valid_q,  E = |c_q - c_p|^2 / (sigma_c 0.5^it)^2 + |n_q - n_p|^2 / sigma_n^2 + |x_q - x_p|^2 / sigma_p^2;
+ * c <- sum(w c_q) / max(sum w, 1e-20) on valid texels (channel sum of img != 0), unchanged elsewhere; result expm1(c) * valid.  Validity is zero outside the
+ * image.  guide_nrm / guide_pos [H,W,3] are optional (NULL, or a sigma of 0, switches the term off; their sigmas do not shrink with the pass): the texel
+ * G-buffers of the IrT stage, which tell neighbours of the same surface from the unrelated chart a padded gutter borders on.
+ * One launch per pass, ping-pong between tmp and out (img, tmp, out [H,W,3]: three different buffers; the result is in out). */
+TEXIR_API int texir_texture_denoise(const float* img /*dev [H,W,3]*/, int32_t H, int32_t W, const float* guide_nrm /*dev, nullable*/,
+                       const float* guide_pos /*dev, nullable*/, int32_t iterations, float sigma_c, float sigma_n, float sigma_p,
+                       float* tmp /*dev [H,W,3]*/, float* out /*dev [H,W,3]*/, void* stream);
+
 /* ---- host-side codec loops of the file formats around the path (both take HOST pointers) ----------------------------
  * PNG scanline un-filtering (filters 0-4, PNG spec 9.2) of zlib-inflated IDAT data: raw [H][stride+1] -> out [H][stride]; replaces the
  * decode half of cv2.imread("0.png", -1) (models/tracer_o3d_irt.py:91, datasets/dataset.py:489-492). */

@@ -86,6 +86,10 @@ def lib():
         L.texir_mip_elems.restype = i64
         L.texir_loss_workspace_bytes.argtypes = [i64, i32, i32]
         L.texir_loss_workspace_bytes.restype = i64
+        L.texir_texture_pad_workspace_bytes.argtypes = [i32, i32]
+        L.texir_texture_pad_workspace_bytes.restype = i64
+        sig["texir_texture_pad"] = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        sig["texir_texture_denoise"] = [vp, i32, i32, vp, vp, i32, f32, f32, f32, vp, vp, vp]
         sig["texir_png_unfilter"] = [vp, i32, i32, i32, vp]
         L.texir_hdr_decode_scanlines.argtypes = [vp, i64, i32, i32, vp]
         L.texir_hdr_decode_scanlines.restype = i64

@@ -612,4 +612,35 @@ int texir_loss_forward(int32_t stage, int32_t loss_type, const float* gt, const 
     return TEXIR_OK;
 }
 
+/* ---- the asset step between the stages (tools/padding_texture.py:49-87), csrc/texpost.hip ---- */
+int64_t texir_texture_pad_workspace_bytes(int32_t H, int32_t W)
+{
+    if (H <= 0 || W <= 0) return 0;
+    return (int64_t)texpost_pad_workspace_bytes(H, W);
+}
+
+int texir_texture_pad(const float* img, int32_t H, int32_t W, int32_t C, const int32_t* row_map, const int32_t* col_map, float* out, int32_t* src,
+                      void* workspace, void* stream)
+{
+    if (!img || !out || !workspace) return fail(TEXIR_ERR_INVALID, "texir_texture_pad: null argument (img, out and workspace are required)");
+    if (out == img) return fail(TEXIR_ERR_INVALID, "texir_texture_pad: out must not be img (holes read other texels of img)");
+    if (C < 1 || C > 4) return fail(TEXIR_ERR_INVALID, "texir_texture_pad: C must be 1..4 (got %d)", C);
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(TEXIR_ERR_INVALID, "texir_texture_pad: H and W must be 1..16384 (got %d x %d)", H, W);
+    if ((row_map == nullptr) != (col_map == nullptr)) return fail(TEXIR_ERR_INVALID, "texir_texture_pad: row_map and col_map go together (both for the reference mode, neither for nearest)");
+    HIP_TRY(launch_texture_pad(img, H, W, C, row_map, col_map, out, src, workspace, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
+int texir_texture_denoise(const float* img, int32_t H, int32_t W, const float* guide_nrm, const float* guide_pos, int32_t iterations, float sigma_c,
+                          float sigma_n, float sigma_p, float* tmp, float* out, void* stream)
+{
+    if (!img || !tmp || !out) return fail(TEXIR_ERR_INVALID, "texir_texture_denoise: null argument (img, tmp and out are required)");
+    if (out == img || tmp == img || tmp == out) return fail(TEXIR_ERR_INVALID, "texir_texture_denoise: img, tmp and out must be three different buffers");
+    if (iterations < 1 || iterations > 6) return fail(TEXIR_ERR_INVALID, "texir_texture_denoise: iterations must be 1..6 (got %d)", iterations);
+    if (H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30) return fail(TEXIR_ERR_INVALID, "texir_texture_denoise: bad size %d x %d", H, W);
+    if (!(sigma_c > 0.0f) || !(sigma_n >= 0.0f) || !(sigma_p >= 0.0f)) return fail(TEXIR_ERR_INVALID, "texir_texture_denoise: sigma_c must be > 0, sigma_n and sigma_p >= 0");
+    HIP_TRY(launch_texture_denoise(img, H, W, guide_nrm, guide_pos, iterations, sigma_c, sigma_n, sigma_p, tmp, out, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 }  // extern "C"

@@ -22,6 +22,7 @@ struct Env {
     int irt_grid_cap;          // TEXIR_IRT_GRID_CAP         0 = every co-resident workgroup (default) | blocks of the persistent IrT grid (256 = one wave per SIMD: occupancy sweeps, tools/chain_probe.py)
     int spec_grid_cap;         // TEXIR_SPEC_GRID_CAP        65536 (default)
     int spec_lpp;              // TEXIR_SPEC_LPP             0 = automatic | forced lanes per pixel (power of two)
+    int atrous_lds_passes;     // TEXIR_ATROUS_LDS_PASSES    -1 = automatic (default) | 0..3: how many of the first a-trous passes read their taps from an LDS tile (texpost.hip; same bits)
 };
 
 const Env& env();          // the current snapshot

@@ -55,4 +55,10 @@ hipError_t launch_adam_tex(float* p, const float* g /*nullable*/, const uint32_t
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int step,
                        float lo, float hi, const float* hyper /*dev, nullable*/, hipStream_t st);
 hipError_t launch_adam_tick(double* state, float* hyper, int n, unsigned long long mask, hipStream_t st);
+// texpost.hip: the pad + denoise step between the two stages (tools/padding_texture.py:49-87)
+size_t texpost_pad_workspace_bytes(int H, int W);
+hipError_t launch_texture_pad(const float* img, int H, int W, int C, const int32_t* row_map, const int32_t* col_map, float* out, int32_t* src, void* workspace,
+                              hipStream_t st);
+hipError_t launch_texture_denoise(const float* img, int H, int W, const float* nrm, const float* pos, int iterations, float sigma_c, float sigma_n, float sigma_p,
+                                  float* tmp, float* out, hipStream_t st);
 }  // namespace texir

@@ -3,9 +3,19 @@ irradiance texture (seams / gutters) take the value of their nearest non-zero te
 mip-mapped fetches near chart borders do not bleed black.  One-time CPU step in the reference (scipy + torch grid_sample); kept
 on the same ops here, including grid_sample's nearest-rounding quirk.  The reference then pipes the padded texture through the
 external Open Image Denoise binary (:86-87); `denoise_atrous` is a stand-in for that call (an edge-avoiding a-trous wavelet
-filter, Dammertz et al. 2010, colour edge-stopping only like OIDN's image-only mode) -- NOT a re-implementation of OIDN's network.
+filter, Dammertz et al. 2010, colour edge-stopping like OIDN's image-only mode, optionally guided by normal / position images) -- NOT a
+re-implementation of OIDN's network.
 
-    python -m texir_code_amd.tools pad <.../0_irr_texture.hdr> [<.../irt.hdr>] [--denoise]
+What the quirk costs.  The reference's fill is NOT a nearest fill: F.grid_sample(mode="nearest") with the default align_corners=False
+un-normalises source index i to i - 0.5 and rounds half to even, so every odd source row or column is read one texel too low -- and
+that texel is often a hole again.  On seeded 96x128 and 100x124 atlases at 55 % occupancy `padding_texture` (= the reference, = mode
+`reference` of the device route) leaves 33 % and 36 % of the hole texels black, and only a quarter of the holes with a unique nearest
+texel receive that texel's value.  Mode `nearest` of the device route (texpost.pad_texture, csrc/texpost.hip) fills every hole from a
+texel at minimal distance; `reference` reproduces this function bit for bit, for those who need the reference's file.
+
+    python -m texir_code_amd.tools pad <.../0_irr_texture.hdr> [<.../irt.hdr>] [--denoise] [--gpu] [--mode nearest|reference]
+
+Without --gpu: this module's CPU path (mode reference; --mode nearest needs --gpu).  With --gpu: texpost on the device, mode nearest unless told.
 """
 import sys
 
@@ -35,10 +45,12 @@ def padding_texture(img):
     return res * mf + img * (1 - mf)
 
 
-def denoise_atrous(img, iterations=3, sigma_c=0.5, device=None):
+def denoise_atrous(img, iterations=3, sigma_c=0.5, device=None, guide_nrm=None, guide_pos=None, sigma_n=0.3, sigma_p=0.25):
     """edge-avoiding a-trous filter on log(1+x): `iterations` passes of the 5x5 B3-spline kernel with hole sizes 1, 2, 4, ... and the
     edge-stopping weight exp(-|dc|^2 / sigma_c^2) (sigma halves every pass).  Zero texels (unpadded seams) neither contribute nor change.
-    Runs on `device` (default: the GPU when present); a 4k x 4k texture takes a few tens of milliseconds there."""
+    guide_nrm / guide_pos [H,W,3] (optional) add |dn|^2 / sigma_n^2 and |dx|^2 / sigma_p^2 to the exponent (a sigma of 0 switches its term off; these
+    two do not shrink with the pass; replicate border like the colour): the texel G-buffers tell the same surface from the unrelated chart across a gutter.
+    Runs on `device` (default: the GPU when present); a 4k x 4k texture takes a few tens of milliseconds there.  texpost.denoise is the fused kernel."""
     if device is None:
         device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
     x = torch.as_tensor(np.asarray(img, np.float32), device=device)
@@ -46,16 +58,26 @@ def denoise_atrous(img, iterations=3, sigma_c=0.5, device=None):
     c = torch.log1p(x.clamp(min=0))
     k1 = torch.tensor([1.0, 4.0, 6.0, 4.0, 1.0], device=device) / 16.0
     H, W, _ = c.shape
+    guides = []
+    for gimg, sg in ((guide_nrm, sigma_n), (guide_pos, sigma_p)):
+        if gimg is not None and sg > 0:
+            guides.append((torch.as_tensor(np.asarray(gimg, np.float32), device=device), sg ** 2))
     for it in range(iterations):
         step, s2 = 1 << it, (sigma_c * 0.5 ** it) ** 2
         acc, wsum = torch.zeros_like(c), torch.zeros((H, W, 1), device=device)
         pad = 2 * step
-        cp = F.pad(c.permute(2, 0, 1)[None], (pad, pad, pad, pad), mode="replicate")[0].permute(1, 2, 0)
+        rep = lambda t: F.pad(t.permute(2, 0, 1)[None], (pad, pad, pad, pad), mode="replicate")[0].permute(1, 2, 0)
+        cp = rep(c)
         vp = F.pad(valid.permute(2, 0, 1)[None], (pad, pad, pad, pad), mode="constant", value=0.0)[0].permute(1, 2, 0)
+        gp = [(gt, rep(gt), g2) for gt, g2 in guides]
         for dy in range(5):
             for dx in range(5):
-                q = cp[dy * step:dy * step + H, dx * step:dx * step + W]
-                w = k1[dy] * k1[dx] * torch.exp(-((q - c) ** 2).sum(-1, keepdim=True) / s2) * vp[dy * step:dy * step + H, dx * step:dx * step + W]
+                win = (slice(dy * step, dy * step + H), slice(dx * step, dx * step + W))
+                q = cp[win]
+                e = ((q - c) ** 2).sum(-1, keepdim=True) / s2
+                for gt, gpad, g2 in gp:
+                    e = e + ((gpad[win] - gt) ** 2).sum(-1, keepdim=True) / g2
+                w = k1[dy] * k1[dx] * torch.exp(-e) * vp[win]
                 acc += q * w
                 wsum += w
         c = torch.where(valid > 0, acc / wsum.clamp(min=1e-20), c)
@@ -63,16 +85,40 @@ def denoise_atrous(img, iterations=3, sigma_c=0.5, device=None):
 
 
 def main(argv):
-    flags = [a for a in argv if a.startswith("--")]
-    argv = [a for a in argv if not a.startswith("--")]
+    flags, rest, mode = [], [], None
+    it = iter(argv)
+    for a in it:
+        if a == "--mode":
+            mode = next(it, None)
+        elif a.startswith("--mode="):
+            mode = a.split("=", 1)[1]
+        elif a.startswith("--"):
+            flags.append(a)
+        else:
+            rest.append(a)
+    argv = rest
     if len(argv) < 2 or argv[0] != "pad":
         print(__doc__)
         return 2
+    gpu = "--gpu" in flags
+    if mode is None:
+        mode = "nearest" if gpu else "reference"
+    if mode not in ("nearest", "reference") or (mode == "nearest" and not gpu):
+        print("--mode must be nearest or reference; nearest needs --gpu (the CPU path is the reference's)")
+        return 2
     src = argv[1]
     dst = argv[2] if len(argv) > 2 else src.replace("0_irr_texture", "irt")
-    out = padding_texture(IO.read_hdr(src))
-    if "--denoise" in flags:
-        out = denoise_atrous(out)
+    if gpu:
+        from . import texpost
+        dev = torch.from_numpy(np.ascontiguousarray(IO.read_hdr(src), np.float32)).cuda()
+        dev = texpost.pad_texture(dev, mode=mode)
+        if "--denoise" in flags:
+            dev = texpost.denoise(dev)
+        out = dev.cpu().numpy()
+    else:
+        out = padding_texture(IO.read_hdr(src))
+        if "--denoise" in flags:
+            out = denoise_atrous(out)
     IO.write_hdr(dst, out)
     print("wrote", dst)
     return 0

@@ -11,11 +11,41 @@ from ..plugin import get_class
 from ..runlog import phases
 
 
+IRT_PAD = ("none", "nearest", "reference")
+IRT_DENOISE = ("none", "color", "guided")
+
+
+def irt_post_settings(conf):
+    """the optional keys of the asset step between the stages (tools/padding_texture.py:49-87, run on the device by texpost):
+      train.irt_pad = none (default: today's behaviour, no irt.hdr) | nearest (every zero texel from a texel at minimal distance) | reference (the
+                      reference's grid_sample rounding bit for bit: about a third of the gutter texels stay black, tools.py);
+      train.irt_denoise = none (default) | color | guided (a-trous filter, guided by the texel G-buffers); needs irt_pad != none;
+      train.irt_denoise_sigma = [sigma_c, sigma_n, sigma_p] (default [0.5, 0.3, 0.25]).
+    -> (pad, denoise, sigma); bad values raise ValueError."""
+    pad = str(conf.get("train.irt_pad", "none")).lower()
+    den = str(conf.get("train.irt_denoise", "none")).lower()
+    if pad not in IRT_PAD:
+        raise ValueError("train.irt_pad must be none, nearest or reference, got %r" % pad)
+    if den not in IRT_DENOISE:
+        raise ValueError("train.irt_denoise must be none, color or guided, got %r" % den)
+    if den != "none" and pad == "none":
+        raise ValueError("train.irt_denoise = %s needs train.irt_pad = nearest or reference (a denoised texture with black gutters is no irt.hdr)" % den)
+    sigma = conf.get("train.irt_denoise_sigma", [0.5, 0.3, 0.25])
+    try:
+        sigma = tuple(float(v) for v in sigma)
+    except (TypeError, ValueError):
+        raise ValueError("train.irt_denoise_sigma must be a list of three numbers, got %r" % (sigma,))
+    if len(sigma) != 3 or not sigma[0] > 0 or sigma[1] < 0 or sigma[2] < 0:
+        raise ValueError("train.irt_denoise_sigma must be [sigma_c > 0, sigma_n >= 0, sigma_p >= 0], got %r" % (sigma,))
+    return pad, den, sigma
+
+
 class IrrTextureRunner:
     def __init__(self, **kwargs):
         torch.set_default_dtype(torch.float32)
         torch.set_num_threads(1)                 # as the reference's runners (e.g. trainer/train_material.py:34): host torch ops are tiny
         self.conf = ConfigFactory.parse_file(kwargs["conf"])
+        self.irt_pad, self.irt_denoise, self.irt_denoise_sigma = irt_post_settings(self.conf)
         self.exps_folder_name = kwargs["exps_folder_name"]
         self.train_batch_size = self.conf.get_int("train.batch_size")
         self.nepochs = self.conf.get_int("train.mat_epoch")
@@ -51,4 +81,25 @@ class IrrTextureRunner:
         if rank == 0:
             with phases.phase("write_hdr", sync=False):
                 IO.write_hdr(target, arr)          # Radiance RGBE (RLE scanlines) like cv2.imwrite('.hdr') (generate_ir_texture.py:82)
+            if self.irt_pad != "none":
+                self._write_irt(irr_texture, target.replace("0_irr_texture.hdr", "irt.hdr"))
         return irr_texture
+
+    def _write_irt(self, irr_texture, path):
+        """the Mat stage's irt.hdr (models.py: MaterialModel reads it) from the assembled device texture: what tools/padding_texture.py:49-87 does to the
+        file between the stages.  Rank 0 only -- every rank holds the whole texture, no collective is added.  Holes are judged on the image (zero texels),
+        not on the seam mask: that is what the reference does to the file."""
+        from .. import texpost
+        with phases.phase("irt_post"):
+            want_src = self.irt_denoise == "guided"
+            res = texpost.pad_texture(irr_texture, mode=self.irt_pad, return_src=want_src)
+            if self.irt_denoise == "color":
+                res = texpost.denoise(res, sigma=self.irt_denoise_sigma)
+            elif self.irt_denoise == "guided":
+                res, src = res
+                nrm = texpost.gather_src(self.model.normal_texture, src)
+                pos = texpost.gather_src(self.model.position_texture, src)
+                res = texpost.denoise(res, nrm=nrm, pos=pos, sigma=self.irt_denoise_sigma)
+            host = torch.empty(res.shape, dtype=res.dtype, pin_memory=True)
+            host.copy_(res)
+            IO.write_hdr(path, host.numpy())

@@ -13,7 +13,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from texir_code_amd import conf as C, dist_util, scene as S, synth, tools  # noqa: E402
+from texir_code_amd import conf as C, dist_util, scene as S, synth  # noqa: E402
 from texir_code_amd.nirf import IRFLoss, TracerO3dIrrF  # noqa: E402
 
 
@@ -87,6 +87,7 @@ def main():
     ap.add_argument("--spp", type=int, default=2048)
     ap.add_argument("--nirf-steps", type=int, default=50)
     ap.add_argument("--mat-steps", type=int, default=50)
+    ap.add_argument("--pad-mode", default="nearest", choices=("nearest", "reference"), help="texpost.pad_texture mode of step 3 (reference: the reference's grid_sample rounding, bit for bit)")
     ap.add_argument("--check", action="store_true", help="verify every stage (tests/test_gpu_scan_and_configs.py): NIrF ground truth and an IrT texel "
                     "sample against the CPU oracle, IrT 8-shard union == whole, material step hipGraph replay == eager call order")
     a = ap.parse_args()
@@ -148,11 +149,15 @@ def main():
     if a.check:
         out["checks"] = checks(a, sc, sc0, m, P, N, vid, d_pos, d_nrm, d_shift, ids, irr, dev)
 
-    # 3. the asset step in between (tools/padding_texture.py) + material step
+    # 3. the asset step in between (tools/padding_texture.py:49-87) on the device (texpost) + material step
+    from texir_code_amd import texpost
+    torch.cuda.synchronize()
     t0 = time.perf_counter()
-    padded = tools.padding_texture(irr.reshape(a.res, a.res, 3).cpu().numpy())
-    out["padding_s"] = round(time.perf_counter() - t0, 2)
-    mat = bench.mat_leg(sc, sc0, torch.from_numpy(padded).to(dev).reshape(-1, 3), a.res, dev, 0, 1, steps=a.mat_steps)
+    padded = texpost.pad_texture(irr.reshape(a.res, a.res, 3), mode=a.pad_mode)
+    torch.cuda.synchronize()
+    out["padding_s"] = round(time.perf_counter() - t0, 4)
+    out["padding_mode"] = a.pad_mode
+    mat = bench.mat_leg(sc, sc0, padded.reshape(-1, 3), a.res, dev, 0, 1, steps=a.mat_steps)
     out["material_step"] = mat
     print(json.dumps(out))
 

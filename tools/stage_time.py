@@ -2,7 +2,7 @@
 (trainer/exp_runner.py:54-80, trainer/generate_ir_texture.py:75-82, trainer/train_material.py:408-605) -- at BASELINE.json's sizes,
 from files on disk to files on disk, with the per-phase breakdown (load, BVH, G-buffer, kernel, download, write ...).
 
-    python tools/stage_time.py [--workload c4] [--root DIR] [--mat-epochs 40] [--no-mat] [--log-lag N] [--keep]         (also: python bench.py --full)
+    python tools/stage_time.py [--workload c4] [--root DIR] [--mat-epochs 40] [--no-mat] [--log-lag N] [--keep] [--irt-post]        (also: python bench.py --full)
 
 The asset set is written first (not timed): a 1 M-triangle out1.obj, a 4096^2 16-bit index PNG, a 4096^2 Radiance hdr_texture.hdr, the exact
 texel G-buffer, 16 cameras, and -- for Mat -- the 16 ground-truth cube views rendered by the product's own forward.  What is timed is what a
@@ -117,7 +117,7 @@ def time_mat(conf_mat, exps, epochs, log_lag, profile=False):
     return out
 
 
-def run(workload="c4", root=None, mat_epochs=40, keep=False, style="room", do_mat=True, log_lag=None, pano_flow=True, profile=False):
+def run(workload="c4", root=None, mat_epochs=40, keep=False, style="room", do_mat=True, log_lag=None, pano_flow=True, profile=False, irt_post=False):
     import torch
     from texir_code_amd import conf as C, datasets as D
     made = root is None
@@ -133,10 +133,17 @@ def run(workload="c4", root=None, mat_epochs=40, keep=False, style="room", do_ma
         torch.zeros(1, device="cuda")                     # context creation is not a phase of the stage
         from texir_code_amd import _lib
         _lib.lib()
+        if irt_post:
+            # the IrrT stage pads + denoises on the device and writes the Mat stage's irt.hdr itself (phase irt_post); the default run keeps the plain copy below
+            txt = open(conf_irt).read()
+            open(conf_irt, "w").write(txt.replace("irt_res = native", "irt_res = native\n    irt_pad = nearest\n    irt_denoise = guided"))
         out["irrt"] = time_irrt(conf_irt)
         out["irrt"]["output"] = os.path.getsize(os.path.join(mesh_dir, "0_irr_texture.hdr"))
         out["irrt"]["texel_gbuffer"] = "file (the synthetic generator's exact texel_gbuffer.npz)"
-        shutil.copy(os.path.join(mesh_dir, "0_irr_texture.hdr"), os.path.join(mesh_dir, "irt.hdr"))         # (Mat's irradiance input: the exact-G-buffer texture)
+        if irt_post:
+            out["irrt"]["irt_hdr"] = os.path.getsize(os.path.join(mesh_dir, "irt.hdr"))
+        else:
+            shutil.copy(os.path.join(mesh_dir, "0_irr_texture.hdr"), os.path.join(mesh_dir, "irt.hdr"))         # (Mat's irradiance input: the exact-G-buffer texture)
         if pano_flow:
             # the reference's own flow (tracer_o3d_irt.py:99-142): per-panorama cube G-buffers -> Cube2Pano -> gather through the index texture's codes
             t0 = time.perf_counter()
@@ -144,7 +151,8 @@ def run(workload="c4", root=None, mat_epochs=40, keep=False, style="room", do_ma
                 seen = D.write_index_texture_from_panoramas(root, conf_irt)
             out["index_texture_prep_s"] = round(time.perf_counter() - t0, 2)
             conf_pano = os.path.join(root, "irt_pano.conf")
-            open(conf_pano, "w").write(open(conf_irt).read().replace("irt_res = native", "irt_res = native\n    texel_gbuffer = pano"))
+            open(conf_pano, "w").write(open(conf_irt).read().replace("\n    irt_pad = nearest\n    irt_denoise = guided", "")          # (irt.hdr stays the first run's)
+                                       .replace("irt_res = native", "irt_res = native\n    texel_gbuffer = pano"))
             out["irrt_pano_gather"] = time_irrt(conf_pano)
             out["irrt_pano_gather"]["texel_gbuffer"] = ("generate_positions (%d panoramas x cube 256 ray-cast G-buffers -> Cube2Pano 1024 x 512) + index-texture gather; "
                                                         "%.3f of the valid texels land within 5 cm of their true position" % (side * side, seen))
@@ -183,8 +191,9 @@ def main():
     ap.add_argument("--profile", action="store_true", help="run the Mat stage once more under cProfile: `mat_profiled.cprofile_tottime`")
     ap.add_argument("--profile-first", action="store_true", help="cProfile the FIRST Mat run of the process instead (first-use costs): `mat.cprofile_tottime`")
     ap.add_argument("--no-pano", action="store_true", help="skip the IrrT run through the panorama G-buffer flow")
+    ap.add_argument("--irt-post", action="store_true", help="IrrT with train.irt_pad = nearest, train.irt_denoise = guided: the stage writes irt.hdr itself (phase irt_post) instead of the copy")
     a = ap.parse_args()
-    print(json.dumps(run(a.workload, a.root, a.mat_epochs, a.keep, a.style, not a.no_mat, a.log_lag, not a.no_pano, "first" if a.profile_first else a.profile)))
+    print(json.dumps(run(a.workload, a.root, a.mat_epochs, a.keep, a.style, not a.no_mat, a.log_lag, not a.no_pano, "first" if a.profile_first else a.profile, a.irt_post)))
 
 
 if __name__ == "__main__":
