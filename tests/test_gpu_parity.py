@@ -297,7 +297,8 @@ def test_render_loss_rejects_non_onehot_masks(golden, tx):
 
 
 def test_texture_fetch_fwd_bwd_vs_torch_restatement(tx):
-    """nvdiffrast-style bilinear / trilinear fetch (restated; parity unpinned) vs the torch-CPU restatement + its autograd"""
+    """nvdiffrast-style bilinear / trilinear fetch (restated; parity unpinned) vs the torch-CPU restatement + its autograd
+    (the per-element float64 comparison at edge shapes, of every form of the path: test_gpu_texture_kernels.py)"""
     from texir_code_amd.texture import texture
     from oracle import ref_torch as RT
     torch.manual_seed(3)
