@@ -40,6 +40,8 @@ def lib():
         L.txo_generate_dir.argtypes = [vp, i32, i32, i32, vp, vp, vp]
         L.txo_irt_generate.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp]
         L.txo_spec_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, C.c_float]
+        L.txo_ray_candidates.argtypes = [vp, vp, vp, vp, i64, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
+        L.txo_ray_candidates.restype = None
         L.txo_num_threads.restype = i32
         L.txo_set_num_threads.argtypes = [i32]
         L.txo_set_num_threads.restype = None
@@ -111,6 +113,31 @@ class Scene:
         else:
             lib().txo_cast_rays_bvh(self.h, _p(org), _p(dir), R, _p(t), _p(pid), _p(uv), _p(counters))
         return t, pid, uv
+
+    CAND_FIELDS = ("t", "u", "v", "minb", "m", "bt", "b0", "b1", "b2", "robust")
+
+    def ray_candidates(self, org, dir, k, u, tiny, dir_bound=None, max_c=16):
+        """double precision, brute force over all triangles: per ray the triangles a float32 watertight tracer may return under the rounding model
+        of tests/trace_cases.py (k, u, tiny: its safety factor, unit roundoff and denormal term; dir_bound [R,3]: how far the traced direction may be
+        from `dir`) -> dict: n [R], overflow [R] bool, any_robust [R] bool, id [R,max_c] (-1: none), one [R,max_c] float64 array per CAND_FIELDS entry,
+        t_rob [R] / id_rob [R]: the closest robust hit.  org, dir: float64 [R,3]"""
+        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3)
+        dir = np.ascontiguousarray(dir, np.float64).reshape(-1, 3)
+        R = org.shape[0]
+        bd = None if dir_bound is None else np.ascontiguousarray(dir_bound, np.float64).reshape(R, 3)
+        n = np.zeros(R, np.int32)
+        fl = np.zeros(R, np.uint8)
+        cid = np.full((R, max_c), -1, np.int32)
+        val = np.full((R, max_c, len(self.CAND_FIELDS)), np.nan)
+        t_rob = np.full(R, np.inf)
+        id_rob = np.full(R, -1, np.int32)
+        if R:
+            lib().txo_ray_candidates(self.h, _p(org), _p(dir), _p(bd), R, max_c, float(k), float(u), float(tiny), _p(n), _p(fl), _p(cid), _p(val),
+                                     _p(t_rob), _p(id_rob))
+        out = {"n": n, "overflow": (fl & 1) != 0, "any_robust": (fl & 2) != 0, "id": cid, "t_rob": t_rob, "id_rob": id_rob}
+        for j, name in enumerate(self.CAND_FIELDS):
+            out[name] = val[:, :, j]
+        return out
 
     def shade_hits(self, t, pid, uv):
         t = _f32(t).reshape(-1)

@@ -588,6 +588,124 @@ TXO_API void txo_spec_forward(const TxoScene *s, const float *normal, const floa
     free(ham);
 }
 
+/* ------------------------------------------------------------------------------------------ */
+/* per-ray CANDIDATE lists in double precision (tests/trace_cases.py holds the derivation)    */
+/* ------------------------------------------------------------------------------------------ */
+/* For every ray, every triangle whose exact barycentrics (w0, w1, w2), plane distance t (units of |dir|) and float32 rounding
+ * model say that a float32 watertight tracer MAY return it:
+ *   smallest barycentric > -m,   t + k * bt > 0,   t - k * bt <= min over robust hits Q of (t_Q + k * bt_Q)
+ * robust hit: smallest barycentric >= m and t - k * bt > 0.
+ * The model: vertices translated to the origin, sheared so that dir becomes +z (dominant axis kz, the two axes after it cyclically),
+ * one rounding (u relative + tiny) per operation; eE_i = what that does to edge function i; edir_i = |d E_i / d dir| . dir_bound.
+ *   m    = k * max_i (eE_i + edir_i) / |det|                       det = E_0 + E_1 + E_2 (the projected area, twice)
+ *   b_i  = (eE_i + edir_i + |w_i| sum_j (eE_j + edir_j)) / |det| + 4 u |w_i| + tiny              (without k)
+ *   bt   = sum_i |Z_i - t| eE_i / |det| + sum_i |w_i| eZ_i + 5 u sum_i |w_i Z_i| + 4 u |t| + tiny + |t| sum_a |n_a| dir_bound_a / |dir . n|
+ * val[r][c] = {t, u, v, smallest barycentric, m, bt, b_0, b_1, b_2, robust}; (u, v) = (w_1, w_2) in the caller's corner order.
+ * Candidates are sorted by t; more than max_c of them (or more than TXO_PRE before the cut at the robust hit) sets flags bit 0.
+ * flags bit 1: the ray has a robust hit; t_rob[r] = the smallest t of a robust hit (+inf: none), id_rob[r] its triangle. */
+#define TXO_PRE 8192
+#define TXO_NV 10
+
+typedef struct { double v[TXO_NV]; int32_t id; } TxoCand;
+
+TXO_API void txo_ray_candidates(const TxoScene *s, const double *org, const double *dir, const double *dir_bound /* [R,3] or NULL */,
+                                int64_t R, int max_c, double k, double u, double tiny,
+                                int32_t *n_cand, uint8_t *flags, int32_t *cid /* [R,max_c] */, double *val /* [R,max_c,TXO_NV] */,
+                                double *t_rob, int32_t *id_rob)
+{
+#pragma omp parallel
+    {
+        TxoCand *pre = (TxoCand *)malloc(sizeof(TxoCand) * TXO_PRE);
+#pragma omp for schedule(dynamic, 16)
+        for (int64_t r = 0; r < R; r++) {
+            const double *o = org + 3 * r, *d = dir + 3 * r;
+            double bd[3] = {0, 0, 0};
+            if (dir_bound) { bd[0] = dir_bound[3 * r]; bd[1] = dir_bound[3 * r + 1]; bd[2] = dir_bound[3 * r + 2]; }
+            n_cand[r] = 0; flags[r] = 0; t_rob[r] = INFINITY; id_rob[r] = -1;
+            for (int c = 0; c < max_c; c++) cid[(size_t)r * max_c + c] = -1;
+            for (int c = 0; c < max_c * TXO_NV; c++) val[(size_t)r * max_c * TXO_NV + c] = NAN;
+            const double ax = fabs(d[0]), ay = fabs(d[1]), az = fabs(d[2]);
+            if (!(isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2])) || !(ax + ay + az > 0.0)) continue;   /* documented: a miss */
+            const int kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2), k1 = (kz + 1) % 3, k2 = (kz + 2) % 3;
+            const double Sz = 1.0 / d[kz], Sx = d[k1] * Sz, Sy = d[k2] * Sz;
+            const double eSz = u * fabs(Sz) + tiny;
+            const double eSx = fabs(d[k1]) * eSz + u * fabs(Sx) + tiny, eSy = fabs(d[k2]) * eSz + u * fabs(Sy) + tiny;
+            int np = 0, over = 0;
+            double tlim = INFINITY;
+            for (int p = 0; p < s->T; p++) {
+                double q[3][3], X[3], Y[3], Z[3], eX[3], eY[3], eZ[3];
+                for (int i = 0; i < 3; i++) {
+                    const float *vp = s->verts + 3 * (size_t)s->tris[3 * (size_t)p + i];
+                    for (int a = 0; a < 3; a++) q[i][a] = (double)vp[a] - o[a];
+                    const double qx = q[i][k1], qy = q[i][k2], qz = q[i][kz];
+                    const double eqx = u * fabs(qx) + tiny, eqy = u * fabs(qy) + tiny, eqz = u * fabs(qz) + tiny;
+                    X[i] = qx - Sx * qz; Y[i] = qy - Sy * qz; Z[i] = Sz * qz;
+                    eX[i] = eqx + fabs(Sx) * eqz + fabs(qz) * eSx + (u * fabs(Sx * qz) + tiny) + (u * fabs(X[i]) + tiny);
+                    eY[i] = eqy + fabs(Sy) * eqz + fabs(qz) * eSy + (u * fabs(Sy * qz) + tiny) + (u * fabs(Y[i]) + tiny);
+                    eZ[i] = fabs(Sz) * eqz + fabs(qz) * eSz + u * fabs(Z[i]) + tiny;
+                }
+                double E[3], eE[3], det = 0.0, nrm[3] = {0, 0, 0};
+                for (int i = 0; i < 3; i++) {
+                    const int b = (i + 1) % 3, c = (i + 2) % 3;      /* E_i = e(B, C) = C.x * B.y - C.y * B.x */
+                    const double p1 = X[c] * Y[b], p2 = Y[c] * X[b];
+                    E[i] = p1 - p2;
+                    eE[i] = fabs(Y[b]) * eX[c] + fabs(X[c]) * eY[b] + fabs(X[b]) * eY[c] + fabs(Y[c]) * eX[b]
+                          + u * (fabs(p1) + fabs(p2)) + u * fabs(E[i]) + 3 * tiny;
+                    /* d E_i / d dir = (q_b x q_c) / dir[kz] up to the sign */
+                    const double cr[3] = {q[b][1] * q[c][2] - q[b][2] * q[c][1], q[b][2] * q[c][0] - q[b][0] * q[c][2], q[b][0] * q[c][1] - q[b][1] * q[c][0]};
+                    eE[i] += (fabs(cr[0]) * bd[0] + fabs(cr[1]) * bd[1] + fabs(cr[2]) * bd[2]) * fabs(Sz);
+                    for (int a = 0; a < 3; a++) nrm[a] += cr[a];
+                    det += E[i];
+                }
+                if (det == 0.0 || !isfinite(det)) continue;
+                const double ad = fabs(det);
+                double w[3], esum = eE[0] + eE[1] + eE[2], emax = fmax(eE[0], fmax(eE[1], eE[2]));
+                for (int i = 0; i < 3; i++) w[i] = E[i] / det;
+                const double minb = fmin(w[0], fmin(w[1], w[2])), m = k * emax / ad;
+                if (!(minb > -m)) continue;
+                const double t = w[0] * Z[0] + w[1] * Z[1] + w[2] * Z[2];
+                double bt = 4 * u * fabs(t) + tiny;
+                /* the rounding part uses the edge functions' rounding errors alone; the direction enters through d t / d dir = -t n / (dir . n) */
+                for (int i = 0; i < 3; i++) {
+                    const int b = (i + 1) % 3, c = (i + 2) % 3;
+                    const double cr[3] = {q[b][1] * q[c][2] - q[b][2] * q[c][1], q[b][2] * q[c][0] - q[b][0] * q[c][2], q[b][0] * q[c][1] - q[b][1] * q[c][0]};
+                    const double edir = (fabs(cr[0]) * bd[0] + fabs(cr[1]) * bd[1] + fabs(cr[2]) * bd[2]) * fabs(Sz);
+                    bt += fabs(Z[i] - t) * (eE[i] - edir) / ad + fabs(w[i]) * eZ[i] + 5 * u * fabs(w[i] * Z[i]);
+                }
+                bt += fabs(t) * (fabs(nrm[0]) * bd[0] + fabs(nrm[1]) * bd[1] + fabs(nrm[2]) * bd[2]) * fabs(Sz) / ad;
+                if (!(t + k * bt > 0.0)) continue;
+                const int robust = minb >= m && t - k * bt > 0.0;
+                if (robust) {
+                    if (t + k * bt < tlim) tlim = t + k * bt;
+                    if (t < t_rob[r]) { t_rob[r] = t; id_rob[r] = p; }
+                }
+                if (np == TXO_PRE) { over = 1; continue; }
+                TxoCand *cd = &pre[np++];
+                cd->id = p;
+                cd->v[0] = t; cd->v[1] = w[1]; cd->v[2] = w[2]; cd->v[3] = minb; cd->v[4] = m; cd->v[5] = bt;
+                for (int i = 0; i < 3; i++) cd->v[6 + i] = (eE[i] + fabs(w[i]) * esum) / ad + 4 * u * fabs(w[i]) + tiny;
+                cd->v[9] = (double)robust;
+            }
+            /* cut at the closest robust hit, sort by t (insertion: the lists are short) */
+            int n = 0;
+            for (int i = 0; i < np; i++) if (pre[i].v[0] - k * pre[i].v[5] <= tlim) pre[n++] = pre[i];
+            for (int i = 1; i < n; i++) {
+                TxoCand x = pre[i]; int j = i - 1;
+                while (j >= 0 && (pre[j].v[0] > x.v[0] || (pre[j].v[0] == x.v[0] && pre[j].id > x.id))) { pre[j + 1] = pre[j]; j--; }
+                pre[j + 1] = x;
+            }
+            if (n > max_c) { over = 1; n = max_c; }
+            for (int i = 0; i < n; i++) {
+                cid[(size_t)r * max_c + i] = pre[i].id;
+                memcpy(val + ((size_t)r * max_c + i) * TXO_NV, pre[i].v, sizeof(double) * TXO_NV);
+            }
+            n_cand[r] = n;
+            flags[r] = (uint8_t)(over | (isfinite(t_rob[r]) ? 2 : 0));
+        }
+        free(pre);
+    }
+}
+
 /* number of OpenMP threads the following calls use (PyTorch's torch.set_num_threads() changes the process-wide default) */
 TXO_API void txo_set_num_threads(int n)
 {

@@ -23,6 +23,7 @@ A sample with k <= 4 uncertain kinks is evaluated in all 2^k branch combinations
   per-pixel sum: inside the sum of its samples' intervals [min over variants - bound, max over variants + bound] plus the accumulation term.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -352,8 +353,15 @@ def reference(inp, ceps=1e-14, mode="spec", names=("w", "dw"), chunk=150000):
     """inp: sample_inputs(...).  mode 'spec' | 'uniform' | 'cosine' | 'importance' (directions only)"""
     M = inp["n"].shape[0]
     ref = Ref(M, names, 1 << MAX_UNC)
-    for a in range(0, M, chunk):
-        _reference_chunk(ref, _take(inp, slice(a, min(M, a + chunk))), a, ceps, mode, names)
+    # (the suite's conftest raises the process-wide OpenMP thread count to every core of the machine for the C oracle; torch shares that setting, and its
+    # many small operations crawl when a job is granted fewer cores than the machine has: keep to what OMP_NUM_THREADS grants while the chain is evaluated)
+    keep = torch.get_num_threads()
+    torch.set_num_threads(min(keep, int(os.environ.get("OMP_NUM_THREADS") or 0) or keep))
+    try:
+        for a in range(0, M, chunk):
+            _reference_chunk(ref, _take(inp, slice(a, min(M, a + chunk))), a, ceps, mode, names)
+    finally:
+        torch.set_num_threads(keep)
     return ref
 
 
