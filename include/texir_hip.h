@@ -387,6 +387,48 @@ TEXIR_API int texir_texture_denoise(const float* img /*dev [H,W,3]*/, int32_t H,
                        const float* guide_pos /*dev, nullable*/, int32_t iterations, float sigma_c, float sigma_n, float sigma_p,
                        float* tmp /*dev [H,W,3]*/, float* out /*dev [H,W,3]*/, void* stream);
 
+/* ---- the texel G-buffer from the mesh: replaces models/tracer_o3d_irt.py:99-142 (generate_positions + calcute_position_normal_texture: a cube map
+ * ray-cast per view, warped to a 1024 x 512 panorama, and a gather of every texel's position through the (row code, column code, panorama id) triple of
+ * 0.png) by a rasterisation of the scene's triangles in uv space.  Needs no index texture; exact per texel instead of quantised to panorama pixels.
+ * Nothing below allocates or synchronises: scratch is the caller's, so the call can be recorded into a hipGraph.
+ *
+ * Texel (r, c) of the H x W atlas, in the hit shader's orientation, has its centre at (u, v) = ((c + 0.5) / W, (r + 0.5) / H) (float32 divisions); the
+ * outputs are in FILE orientation: that texel is row H - 1 - r of pos, nrm, prim_id and bary (what texel_gbuffer.npz holds).  H, W in 1..16384.
+ * The uvs are the scene's tri_uvs as given (V not flipped, no wrap); the atlas is [0,1]^2, what lies outside is clipped.
+ *   COVERAGE: the texel belongs to a triangle when its centre is inside the uv triangle, either winding.  Each edge is evaluated from its two endpoints
+ *     in one canonical order -- (x0, y0) the lexicographically smaller (x, then y) of the two -- in separately rounded float32 operations:
+ *         E = (x1 - x0) * (v - y0) - (y1 - y0) * (u - x0)
+ *     and when that difference is 0 its sign is taken from the exact error terms of the two products, so E == 0 exactly when the rounded operands say so.
+ *     The two triangles sharing an edge thus see the identical E with opposite orientation: exact negations.  With s = the sign of the triangle's area
+ *     (the same evaluation, edge (corner 0, corner 1) at corner 2) and e = +-E the value for the edge as the triangle runs through it, the centre is
+ *     inside the edge when s e > 0, or -- CRACK RULE -- s e == 0 and the edge's inward normal (nx, ny) = s (-(yb - ya), xb - xa) has nx > 0, or nx == 0
+ *     and ny > 0: a centre exactly on an interior chart edge goes to exactly one of the two triangles.  A triangle with zero area (s == 0) or a
+ *     non-finite uv covers nothing.  A triangle is tested against the texels of its clipped bounding box only, columns max(0, floor(umin W - 0.5)) ..
+ *     min(W - 1, ceil(umax W - 0.5)), rows likewise: no centre inside or on the border of the triangle is outside that box.
+ *     OVERLAP RULE: where several triangles cover a centre the lowest primitive id (row of the caller's index array) wins.
+ *     The result is a pure function of (verts, tris, tri_uvs, H, W): integer atomicMin of the primitive id per texel, then one resolve pass; no float
+ *     atomics; identical bits run to run, whatever the launch shape.
+ *   ROUNDING BOUND of the edge function: the centre's coordinates carry one rounding each, every subtraction and product one, the difference one; to first
+ *     order the computed E differs from the exact edge function of the float32 uvs at the exact centre by at most
+ *         |dE| <= |x1 - x0| (4 |v - y0| + |v|) 2^-24 + |y1 - y0| (4 |u - x0| + |u|) 2^-24,
+ *     i.e. in units of uv distance from the edge (E over the edge's length) by at most m = (8 D + 2) 2^-24, D = the largest coordinate difference between
+ *     a centre and an endpoint.  For uvs within [-1, 2] that is 18 x 2^-24 < 2^-19; 2^-18 holds up to D = 7.75.  A triangle the exact arithmetic puts
+ *     a centre more than m inside owns it here unless a lower id does; one it puts more than m outside never does.
+ *   ATTRIBUTES of the winner: e_k = the edge value opposite the CALLER's corner k (the library's stored corner rotation is turned back), S = (e_0 + e_1) + e_2,
+ *     bary = (b1, b2) = (e_1 / S, e_2 / S): the weights of corners 1 and 2, texir_trace_shade's prim_uv convention;
+ *     p = (P0 + b1 (P1 - P0)) + b2 (P2 - P0);  normal_mode TEXIR_NORMAL_GEOMETRIC: n = cross(P1 - P0, P2 - P0) / |cross| (what synth.make_texel_gbuffer
+ *     stores); TEXIR_NORMAL_SHADING: n = (N0 + b1 (N1 - N0)) + b2 (N2 - N0) of the corner normals of texir_scene_set_corner_normals, NOT renormalised
+ *     (:105-106; an error when none are set);  pos = p + offset n (:110: offset 1e-2), nrm = n.  All float32, separately rounded.
+ *     SEAMS: an uncovered texel, and one whose winner has a geometric normal of zero or non-finite length or S == 0, gets pos = nrm = 0, bary = 0,
+ *     prim_id = 0xFFFFFFFF (:137-139 zeroes the seams of the index texture; here the seams are the texels no triangle covers).
+ *   workspace: texir_texel_gbuffer_workspace_bytes bytes of device scratch (4 bytes per texel + 16 per triangle slot + 4 per triangle). */
+#define TEXIR_NORMAL_GEOMETRIC 0
+#define TEXIR_NORMAL_SHADING 1
+TEXIR_API int texir_texel_gbuffer_workspace_bytes(const texir_scene* scene, int32_t H, int32_t W, int64_t* bytes);
+TEXIR_API int texir_texel_gbuffer(const texir_scene* scene, int32_t H, int32_t W, int32_t normal_mode, float offset, float* pos /*dev [H,W,3]*/,
+                       float* nrm /*dev [H,W,3]*/, uint32_t* prim_id /*dev [H,W], nullable*/, float* bary /*dev [H,W,2], nullable*/,
+                       void* workspace /*dev*/, void* stream);
+
 /* ---- host-side codec loops of the file formats around the path (both take HOST pointers) ----------------------------
  * PNG scanline un-filtering (filters 0-4, PNG spec 9.2) of zlib-inflated IDAT data: raw [H][stride+1] -> out [H][stride]; replaces the
  * decode half of cv2.imread("0.png", -1) (models/tracer_o3d_irt.py:91, datasets/dataset.py:489-492). */

@@ -643,4 +643,29 @@ int texir_texture_denoise(const float* img, int32_t H, int32_t W, const float* g
     return TEXIR_OK;
 }
 
+/* ---- the texel G-buffer from the mesh (tracer_o3d_irt.py:99-142), csrc/texraster.hip ---- */
+int texir_texel_gbuffer_workspace_bytes(const texir_scene* s, int32_t H, int32_t W, int64_t* bytes)
+{
+    if (!s || !bytes) return fail(TEXIR_ERR_INVALID, "texir_texel_gbuffer_workspace_bytes: null argument");
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(TEXIR_ERR_INVALID, "texir_texel_gbuffer_workspace_bytes: H and W must be 1..16384 (got %d x %d)", H, W);
+    *bytes = (int64_t)texel_raster_workspace_bytes(s->n_slots, s->n_tris, H, W);
+    return TEXIR_OK;
+}
+
+int texir_texel_gbuffer(const texir_scene* s, int32_t H, int32_t W, int32_t normal_mode, float offset, float* pos, float* nrm, uint32_t* prim_id, float* bary,
+                        void* workspace, void* stream)
+{
+    if (!s || !pos || !nrm || !workspace) return fail(TEXIR_ERR_INVALID, "texir_texel_gbuffer: null argument (scene, pos, nrm and workspace are required)");
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(TEXIR_ERR_INVALID, "texir_texel_gbuffer: H and W must be 1..16384 (got %d x %d)", H, W);
+    if (normal_mode != TEXIR_NORMAL_GEOMETRIC && normal_mode != TEXIR_NORMAL_SHADING)
+        return fail(TEXIR_ERR_INVALID, "texir_texel_gbuffer: normal_mode must be TEXIR_NORMAL_GEOMETRIC (0) or TEXIR_NORMAL_SHADING (1), got %d", normal_mode);
+    if (normal_mode == TEXIR_NORMAL_SHADING && !s->d_cnrm)
+        return fail(TEXIR_ERR_INVALID, "texir_texel_gbuffer: shading normals asked for but texir_scene_set_corner_normals has not been called");
+    if (!(offset - offset == 0.0f)) return fail(TEXIR_ERR_INVALID, "texir_texel_gbuffer: offset must be finite");
+    if (!s->d_uvs) return fail(TEXIR_ERR_INVALID, "texir_texel_gbuffer: the scene has no corner uvs");
+    HIP_TRY(launch_texel_raster(dev_of(s), (const float4*)s->d_cnrm, s->n_slots, s->n_tris, H, W, normal_mode == TEXIR_NORMAL_SHADING, offset, pos, nrm, prim_id,
+                                bary, workspace, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 }  // extern "C"

@@ -61,4 +61,8 @@ hipError_t launch_texture_pad(const float* img, int H, int W, int C, const int32
                               hipStream_t st);
 hipError_t launch_texture_denoise(const float* img, int H, int W, const float* nrm, const float* pos, int iterations, float sigma_c, float sigma_n, float sigma_p,
                                   float* tmp, float* out, hipStream_t st);
+// texraster.hip: the texel G-buffer as a uv-space rasterisation of the mesh (tracer_o3d_irt.py:99-142)
+size_t texel_raster_workspace_bytes(int64_t n_slots, int64_t T, int H, int W);
+hipError_t launch_texel_raster(const SceneDev& sc, const float4* cnrm /*nullable unless shading*/, int64_t n_slots, int64_t T, int H, int W, int shading, float offset,
+                               float* pos, float* nrm, uint32_t* prim_id /*nullable*/, float* bary /*nullable*/, void* workspace, hipStream_t st);
 }  // namespace texir

@@ -13,6 +13,35 @@ def set_corner_normals(scene, corner_normals):
     _lib.check(_lib.lib().texir_scene_set_corner_normals(scene.h, _lib.ptr(a)))
 
 
+NORMAL_MODES = {"geometric": 0, "shading": 1}
+
+
+def raster_texel_gbuffer(scene, H, W, normal="geometric", offset=1e-2, want_ids=False):
+    """The texel G-buffer of an H x W atlas as a uv-space rasterisation of the scene's triangles (texir_texel_gbuffer, csrc/texraster.hip; replaces
+    tracer_o3d_irt.py:99-142 and needs no index texture).  Returns device tensors in FILE orientation (what texel_gbuffer.npz holds):
+    pos [H,W,3] = surface point + offset * normal, nrm [H,W,3]; uncovered texels are all-zero seams.  normal = "geometric" (face normal) or
+    "shading" (interpolated corner normals of set_corner_normals, not renormalised).  want_ids adds prim_id [H,W] int64 (-1: seam) and
+    bary [H,W,2] (weights of the caller's corners 1 and 2).  Launches on the current stream without synchronising it."""
+    if normal not in NORMAL_MODES:
+        raise ValueError("raster_texel_gbuffer: normal must be geometric or shading, got %r" % (normal,))
+    H, W = int(H), int(W)
+    dev = scene.device
+    L = _lib.lib()
+    import ctypes as C
+    nb = C.c_int64()
+    _lib.check(L.texir_texel_gbuffer_workspace_bytes(scene.h, H, W, C.byref(nb)))
+    ws = torch.empty(max(1, int(nb.value)), device=dev, dtype=torch.uint8)
+    pos = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
+    nrm = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
+    ids = torch.empty((H, W), device=dev, dtype=torch.int32) if want_ids else None
+    bary = torch.empty((H, W, 2), device=dev, dtype=torch.float32) if want_ids else None
+    _lib.check(L.texir_texel_gbuffer(scene.h, H, W, NORMAL_MODES[normal], float(offset), _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(ids), _lib.ptr(bary),
+                                     _lib.ptr(ws), _lib.stream_ptr()))
+    if want_ids:
+        return pos, nrm, ids.long(), bary          # (0xFFFFFFFF reads as int32 -1)
+    return pos, nrm
+
+
 def cast_gbuffer(scene, mvp, cube_res, flip_v=False):
     """mvp [6,4,4] (row-vector convention, datasets/dataset.py:464-465) -> dict of [6,c,c,k] tensors:
     position, normal, mask, uv (texc), uv_da (texd), tri_id"""

@@ -97,13 +97,32 @@ class TracerO3d(nn.Module):
         #   reference          what its call computes: cv2.INTER_NEAREST sits in the `dst` slot, so cv2 interpolates the uint16 codes with its default
         #                      INTER_LINEAR -- blended codes between texels of different panoramas included; identical to `nearest` when 0.png
         #                      already has the target size, bit-for-bit the reference's texture otherwise (imgops.resize_u16_as_cv2_default).
-        with phases.phase("load_index_texture", sync=False):
-            idx = IO.read_index_texture(_sibling(self.path_traced_mesh, "0.png"))
-        res = conf.get("train.irt_res", 1024)
+        # train.texel_gbuffer (optional key): auto (default: the file when it exists, else pano) | file | pano | raster.  `raster` rasterises the mesh in uv
+        # space on the device (gbuffer.raster_texel_gbuffer): exact per texel, seams = the texels no triangle covers, and 0.png becomes optional -- without
+        # it the atlas is train.irt_res x train.irt_res.  train.texel_normal = geometric (default) | shading picks the normal the raster route stores.
+        self.use_texel_gbuffer = conf.get("train.texel_gbuffer", "auto")
+        self.raster = isinstance(self.use_texel_gbuffer, str) and self.use_texel_gbuffer == "raster"
+        self.texel_normal = str(conf.get("train.texel_normal", "geometric")).lower()
+        if self.raster and self.texel_normal not in GB.NORMAL_MODES:
+            raise ValueError("train.texel_normal must be geometric or shading, got %r" % self.texel_normal)
+        idx_path = _sibling(self.path_traced_mesh, "0.png")
+        idx = None
+        if not (self.raster and not os.path.exists(idx_path)):
+            with phases.phase("load_index_texture", sync=False):
+                idx = IO.read_index_texture(idx_path)
+        res = conf.get("train.irt_res", 1024 if idx is not None else None)
         how = str(conf.get("train.irt_resize", "nearest")).lower()
         if how not in ("nearest", "reference"):
             raise ValueError("train.irt_resize must be nearest or reference, got %r" % how)
-        if res not in (None, 0, "0", "native"):
+        if idx is None:
+            try:
+                if isinstance(res, bool) or int(res) != float(res) or int(res) < 1:
+                    raise ValueError
+                res = int(res)
+            except (TypeError, ValueError):
+                raise ValueError("train.irt_res must be an integer atlas size when train.texel_gbuffer = raster runs without 0.png (got %r)" % (res,))
+            self.atlas_hw = (res, res)
+        elif res not in (None, 0, "0", "native"):
             res = int(res)
             if (res, res) != idx.shape[:2]:
                 if how == "reference":
@@ -115,10 +134,11 @@ class TracerO3d(nn.Module):
                     ry = (np.arange(res) * idx.shape[0] // res)
                     rx = (np.arange(res) * idx.shape[1] // res)
                     idx = idx[ry][:, rx]
-        self.index_texture = np.ascontiguousarray(idx)
+        self.index_texture = None if idx is None else np.ascontiguousarray(idx)
+        if idx is not None:
+            self.atlas_hw = tuple(int(v) for v in idx.shape[:2])
         # optional exact texel G-buffer written by the synthetic generator (bypasses the panorama gather)
         self.texel_gbuffer_path = _sibling(self.path_traced_mesh, "texel_gbuffer.npz")
-        self.use_texel_gbuffer = conf.get("train.texel_gbuffer", "auto")
 
     # -- tracer_o3d_irt.py:99-112 -----------------------------------------------------------------------------------
     def generate_positions(self):
@@ -159,18 +179,24 @@ class TracerO3d(nn.Module):
 
     # -- tracer_o3d_irt.py:145-180 ----------------------------------------------------------------------------------
     def forward(self):
-        use_file = self.use_texel_gbuffer in (True, "file") or (self.use_texel_gbuffer == "auto" and os.path.exists(self.texel_gbuffer_path))
+        use_file = not self.raster and (self.use_texel_gbuffer in (True, "file") or (self.use_texel_gbuffer == "auto" and os.path.exists(self.texel_gbuffer_path)))
         # The per-texel shifts (33.5 M floats from the CPU generator at 4096^2: 0.2 s) are drawn on a helper thread WHILE the texel G-buffer is loaded / ray-cast:
         # nothing else touches the generator in between, so the stream is the reference's (one [nt,1,2] draw = its torch.rand(512,1,2) per 512-texel batch,
         # sample_util.py:102).  The texel count is the index texture's; if the G-buffer turns out to have another size the generator is put back and the draw redone.
         import threading
-        nt0 = int(self.index_texture.shape[0]) * int(self.index_texture.shape[1])
+        nt0 = self.atlas_hw[0] * self.atlas_hw[1]
         rng_before = torch.get_rng_state()
         early = {}
         th = threading.Thread(target=lambda: early.__setitem__("shift", torch.rand(nt0, 1, 2)), name="texir-irt-shifts", daemon=True)
         th.start()
         with phases.phase("texel_gbuffer"):
-            if use_file:
+            raster_seam = None
+            if self.raster:
+                # tracer_o3d_irt.py:99-142 as one rasterisation of the mesh in uv space; the seams are the texels no triangle covers
+                self.position_texture, self.normal_texture, prim, _ = GB.raster_texel_gbuffer(self.scene, self.atlas_hw[0], self.atlas_hw[1],
+                                                                                            normal=self.texel_normal, offset=1e-2, want_ids=True)
+                raster_seam = (prim < 0).reshape(-1)
+            elif use_file:
                 self._load_texel_gbuffer()
             else:
                 self.generate_positions()
@@ -188,7 +214,7 @@ class TracerO3d(nn.Module):
                 torch.set_rng_state(rng_before)
                 early["shift"] = torch.rand(nt, 1, 2)
             shift = early.pop("shift").reshape(nt, 2).to(self.device, non_blocking=True)
-            seam = torch.from_numpy(seam_texels(self.index_texture).reshape(-1)).to(self.device)
+            seam = raster_seam if raster_seam is not None else torch.from_numpy(seam_texels(self.index_texture).reshape(-1)).to(self.device)
             ids = dist_util.morton_order(torch.nonzero(~seam)[:, 0].to(torch.int32), W)
             rank, world, _ = dist_util.world_info()
             ids_all = ids

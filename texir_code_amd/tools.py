@@ -16,6 +16,11 @@ texel at minimal distance; `reference` reproduces this function bit for bit, for
     python -m texir_code_amd.tools pad <.../0_irr_texture.hdr> [<.../irt.hdr>] [--denoise] [--gpu] [--mode nearest|reference]
 
 Without --gpu: this module's CPU path (mode reference; --mode nearest needs --gpu).  With --gpu: texpost on the device, mode nearest unless told.
+
+    python -m texir_code_amd.tools texel-gbuffer <.../out1.obj> <res> [<.../texel_gbuffer.npz>] [--normal geometric|shading]
+
+The texel G-buffer of any uv-mapped mesh (position + 1e-2 * normal, normal; zero on the texels no triangle covers), rasterised in uv space on the
+device (gbuffer.raster_texel_gbuffer) and written in the format train.texel_gbuffer = file reads.  <res> is the atlas size, or HxW.
 """
 import sys
 
@@ -84,19 +89,50 @@ def denoise_atrous(img, iterations=3, sigma_c=0.5, device=None, guide_nrm=None, 
     return (torch.expm1(c) * valid).cpu().numpy()
 
 
+def write_texel_gbuffer(path_obj, H, W, dst, normal="geometric", device=0):
+    """out1.obj -> texel_gbuffer.npz (position, normal [H,W,3] float32 in file orientation); returns the number of covered texels"""
+    from . import gbuffer as GB
+    from .scene import Scene
+    obj = IO.load_obj(path_obj)
+    scene = Scene(obj["vertices"], obj["indices"], IO.triangle_uvs_open3d(obj), np.zeros((2, 2, 3), np.float32), device=device)     # (no radiance is read)
+    if normal == "shading":
+        GB.set_corner_normals(scene, IO.corner_normals(obj))
+    pos, nrm, prim, _ = GB.raster_texel_gbuffer(scene, H, W, normal=normal, want_ids=True)
+    np.savez(dst, position=pos.cpu().numpy(), normal=nrm.cpu().numpy())
+    return int((prim >= 0).sum().item())
+
+
 def main(argv):
-    flags, rest, mode = [], [], None
+    flags, rest, mode, normal = [], [], None, "geometric"
     it = iter(argv)
     for a in it:
         if a == "--mode":
             mode = next(it, None)
         elif a.startswith("--mode="):
             mode = a.split("=", 1)[1]
+        elif a == "--normal":
+            normal = next(it, None)
+        elif a.startswith("--normal="):
+            normal = a.split("=", 1)[1]
         elif a.startswith("--"):
             flags.append(a)
         else:
             rest.append(a)
     argv = rest
+    if len(argv) >= 3 and argv[0] == "texel-gbuffer":
+        try:
+            hw = [int(v) for v in argv[2].lower().split("x")]
+            H, W = (hw[0], hw[0]) if len(hw) == 1 else hw
+        except ValueError:
+            print("<res> must be an integer or HxW, got %r" % argv[2])
+            return 2
+        if normal not in ("geometric", "shading"):
+            print("--normal must be geometric or shading")
+            return 2
+        dst = argv[3] if len(argv) > 3 else argv[1].replace("out1.obj", "texel_gbuffer.npz") if "out1.obj" in argv[1] else "texel_gbuffer.npz"
+        n = write_texel_gbuffer(argv[1], H, W, dst, normal)
+        print("wrote %s (%d x %d, %d texels covered)" % (dst, H, W, n))
+        return 0
     if len(argv) < 2 or argv[0] != "pad":
         print(__doc__)
         return 2

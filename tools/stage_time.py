@@ -2,7 +2,7 @@
 (trainer/exp_runner.py:54-80, trainer/generate_ir_texture.py:75-82, trainer/train_material.py:408-605) -- at BASELINE.json's sizes,
 from files on disk to files on disk, with the per-phase breakdown (load, BVH, G-buffer, kernel, download, write ...).
 
-    python tools/stage_time.py [--workload c4] [--root DIR] [--mat-epochs 40] [--no-mat] [--log-lag N] [--keep] [--irt-post]        (also: python bench.py --full)
+    python tools/stage_time.py [--workload c4] [--root DIR] [--mat-epochs 40] [--no-mat] [--log-lag N] [--keep] [--irt-post] [--raster]        (also: python bench.py --full)
 
 The asset set is written first (not timed): a 1 M-triangle out1.obj, a 4096^2 16-bit index PNG, a 4096^2 Radiance hdr_texture.hdr, the exact
 texel G-buffer, 16 cameras, and -- for Mat -- the 16 ground-truth cube views rendered by the product's own forward.  What is timed is what a
@@ -117,7 +117,7 @@ def time_mat(conf_mat, exps, epochs, log_lag, profile=False):
     return out
 
 
-def run(workload="c4", root=None, mat_epochs=40, keep=False, style="room", do_mat=True, log_lag=None, pano_flow=True, profile=False, irt_post=False):
+def run(workload="c4", root=None, mat_epochs=40, keep=False, style="room", do_mat=True, log_lag=None, pano_flow=True, profile=False, irt_post=False, raster=False):
     import torch
     from texir_code_amd import conf as C, datasets as D
     made = root is None
@@ -156,6 +156,14 @@ def run(workload="c4", root=None, mat_epochs=40, keep=False, style="room", do_ma
             out["irrt_pano_gather"] = time_irrt(conf_pano)
             out["irrt_pano_gather"]["texel_gbuffer"] = ("generate_positions (%d panoramas x cube 256 ray-cast G-buffers -> Cube2Pano 1024 x 512) + index-texture gather; "
                                                         "%.3f of the valid texels land within 5 cm of their true position" % (side * side, seen))
+        if raster:
+            # the same stage with the G-buffer rasterised from the mesh in uv space (train.texel_gbuffer = raster): neither texel_gbuffer.npz nor the codes of 0.png are read
+            conf_raster = os.path.join(root, "irt_raster.conf")
+            open(conf_raster, "w").write(open(conf_irt).read().replace("\n    irt_pad = nearest\n    irt_denoise = guided", "")
+                                         .replace("irt_res = native", "irt_res = native\n    texel_gbuffer = raster"))
+            out["irrt_raster"] = time_irrt(conf_raster)
+            out["irrt_raster"]["texel_gbuffer"] = "raster (texir_texel_gbuffer: the mesh rasterised in uv space on the device)"
+            out["texel_gbuffer_phase_s"] = {k: out[k]["phases_s"].get("texel_gbuffer") for k in ("irrt", "irrt_pano_gather", "irrt_raster") if k in out}
         if do_mat:
             D.write_conf(conf_mat, root, cube_res=cube, spp=(spp, S), albedo_res=mres, rough_res=mres, epochs=mat_epochs, model="mat")
             txt = open(conf_mat).read().replace("plot_freq = 1000", "plot_freq = 10")
@@ -192,8 +200,10 @@ def main():
     ap.add_argument("--profile-first", action="store_true", help="cProfile the FIRST Mat run of the process instead (first-use costs): `mat.cprofile_tottime`")
     ap.add_argument("--no-pano", action="store_true", help="skip the IrrT run through the panorama G-buffer flow")
     ap.add_argument("--irt-post", action="store_true", help="IrrT with train.irt_pad = nearest, train.irt_denoise = guided: the stage writes irt.hdr itself (phase irt_post) instead of the copy")
+    ap.add_argument("--raster", action="store_true", help="also run IrrT with train.texel_gbuffer = raster (`irrt_raster`; `texel_gbuffer_phase_s` puts the three routes' phases side by side)")
     a = ap.parse_args()
-    print(json.dumps(run(a.workload, a.root, a.mat_epochs, a.keep, a.style, not a.no_mat, a.log_lag, not a.no_pano, "first" if a.profile_first else a.profile, a.irt_post)))
+    print(json.dumps(run(a.workload, a.root, a.mat_epochs, a.keep, a.style, not a.no_mat, a.log_lag, not a.no_pano, "first" if a.profile_first else a.profile, a.irt_post,
+                         a.raster)))
 
 
 if __name__ == "__main__":
