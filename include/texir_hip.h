@@ -126,7 +126,9 @@ TEXIR_API int texir_generate_dir(const float* normals /*dev*/, const float* roug
  *   Long lists (>= 32768 texels) use a stream-ordered scratch allocation (hipMallocAsync/hipFreeAsync on `stream`,
  *     384 bytes per listed texel at N >= 2048) for the per-pass-range partial sums.
  *   stats [8] u64 dev, nullable: += rays, 64-byte node fetches, triangle tests, hits, wave-level node steps, wave-level
- *   triangle steps (how often a wavefront executed each loop body: lane utilisation = lane count / (64 * wave count)), 2 reserved. */
+ *   triangle steps (how often a wavefront executed each loop body: lane utilisation = lane count / (64 * wave count)), [6] stack entries
+ *   dropped by culling when they were popped (their entry distance was not below the closest hit by then; per lane), [7] pushes + pops that
+ *   went through the private overflow part of the traversal stack (depth beyond the LDS part: 10 entries in the IrT kernels; per lane). */
 TEXIR_API int texir_irt_generate(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/,
                        const float* shift /*dev*/, const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids,
                        int64_t Nt, int32_t N, int32_t mode, float* irr /*dev*/, uint64_t* stats /*dev, nullable*/,

@@ -264,7 +264,8 @@ __device__ __forceinline__ float edge2_exact(float bx, float by, float cx, float
 
 // ------------------------------------------------------------------------------------------------
 // closest-hit traversal, one ray per lane.  Stack: LSTK entries per lane in LDS laid out
-// [entry][thread] (conflict-free ds_read/write), deeper entries in a private overflow array.
+// [entry][thread] (conflict-free ds_read/write), deeper entries in a private overflow array.  While the stacks of a wave's lanes stay inside the
+// LDS part, a pop that culls reads the top entry whole and then two entries per LDS round trip (pop_lds).
 // Returns hit triangle slot (leaf order) or -1; t in units of |dir| (Embree semantics: t > 0).
 // ------------------------------------------------------------------------------------------------
 struct Hit { float t, u, v; int slot; };
@@ -317,6 +318,12 @@ constexpr int kProbeSlots = 11;
 #define TEXIR_SCHED_NODE_WEIGHT 2
 #endif
 constexpr int kSchedNodeWeight = TEXIR_SCHED_NODE_WEIGHT;
+// TEXIR_STACK_DRAIN2 (A/B switch; 1 = default): the culling pop of the all-in-LDS paths (trace_core's pop_lds) examines two stack entries per LDS round trip.
+#ifndef TEXIR_STACK_DRAIN2
+#define TEXIR_STACK_DRAIN2 1
+#endif
+// wave_iters[kWiCulled / kWiOverflow] (STATS; per LANE, unlike the wave-level slots before them): stats[6] and stats[7] of include/texir_hip.h
+constexpr int kWiCulled = 2 + kProbeSlots, kWiOverflow = 3 + kProbeSlots, kWiSlots = 4 + kProbeSlots;
 
 // CULL: a stack entry also carries the child's entry distance, and an entry whose distance is not below the closest hit found
 // since it was pushed is dropped when it is popped (it cannot contain a closer hit: same result, bit for bit) instead of
@@ -406,12 +413,16 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
     Entry* const lim = base + LSTK * kBlock;
     Entry* top = base;
     auto make = [](int code, float tn) -> Entry { if constexpr (CULL) return make_int2(code, __float_as_int(tn)); else return code; };
+    // (STATS, per lane: entries dropped by culling; pushes and pops that went through the private overflow array)
+    auto count_culled = [&](uint32_t n) __attribute__((always_inline)) { if constexpr (STATS) { if (wave_iters) wave_iters[kWiCulled] += n; } };
+    auto count_ovf = [&]() __attribute__((always_inline)) { if constexpr (STATS) { if (wave_iters && top >= lim) wave_iters[kWiOverflow]++; } };
     // LDS part and private overflow are kept in separate, wave-uniformly guarded code paths: the overflow is almost never
     // touched (depth > LSTK), and hipcc must not merge the two address spaces into one flat access
     auto push = [&](int code, float tn) {
         const Entry x = make(code, tn);
         if (top < lim) *top = x;
         if (__any(top >= lim)) { if (top >= lim) ovf[(top - lim) / kBlock] = x; }
+        count_ovf();
         top += kBlock;
     };
     auto pop = [&]() -> int {
@@ -420,9 +431,53 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             top -= kBlock;
             Entry v = *(top < lim ? top : lim - kBlock);
             if (__any(top >= lim)) { Entry b = ovf[top >= lim ? (top - lim) / kBlock : 0]; v = top >= lim ? b : v; }
-            if constexpr (CULL) { if (__int_as_float(v.y) < h.t) return v.x; }      // else: behind the closest hit, drop it
+            count_ovf();
+            if constexpr (CULL) { if (__int_as_float(v.y) < h.t) return v.x; count_culled(1u); }      // else: behind the closest hit, drop it
             else return v;
         }
+    };
+    // The culling pop with every entry of the lane in LDS (the caller's wave-uniform guard).  Once a ray has found its hit most of its stack is dead, and the
+    // whole wave waits while one lane drains it.  The top entry is read whole (code and distance: one round trip for a pop that visits); behind it the
+    // entries are examined TWO per round trip: the two entries below `top` lie kBlock * 8 bytes apart (one ds_read2st64_b64), and the upper one is looked at
+    // first, as a loop over single entries would -- the same entries are dropped and the same one is visited.  With one entry left the pair is (slot 0,
+    // slot 1) and slot 1 -- free space inside the lane's column, never an address below `base` -- is ignored.
+    auto pop_lds = [&]() __attribute__((always_inline)) -> int {
+        static_assert(!CULL || LSTK >= 2, "the paired read needs two LDS slots per lane");
+        if constexpr (CULL) {
+            // (the read is issued for every lane, from slot 0 where the stack is empty, instead of inside an exec-mask region of its own; the wave-uniform test
+            // repeats the callers' guard -- with it irt_group_kernel keeps its 800 bytes of scratch per lane, without it the register allocator takes 816)
+            Entry e0 = Entry();
+            if (!__any(top > lim)) e0 = *(top == base ? base : top - kBlock);
+            if (top == base) return kSentinel;
+            top -= kBlock;
+            if (__int_as_float(e0.y) < h.t) return e0.x;
+            count_culled(1u);
+            int n = kSentinel;
+#if TEXIR_STACK_DRAIN2
+            // (one exit, selects inside: the two loads are issued together and unconditionally -- the empty asm keeps the compiler from splitting them into
+            // a distance read, a branch and a code read per entry)
+            bool more = top != base;
+            while (more) {
+                const bool two = top != base + kBlock;
+                Entry* const lo = two ? top - 2 * kBlock : base;
+                Entry el = lo[0], eu = lo[kBlock];
+                asm volatile("" : "+v"(el.x), "+v"(el.y), "+v"(eu.x), "+v"(eu.y));
+                const bool au = two & (__int_as_float(eu.y) < h.t), al = __int_as_float(el.y) < h.t;
+                count_culled(au ? 0u : (two ? 1u : 0u) + (al ? 0u : 1u));
+                top = au ? top - kBlock : lo;
+                n = au ? eu.x : (al ? el.x : n);
+                more = !(au | al) & (top != base);
+            }
+#else
+            while (top != base) {
+                top -= kBlock;
+                const Entry e = *top;
+                if (__int_as_float(e.y) < h.t) { n = e.x; break; }
+                count_culled(1u);
+            }
+#endif
+            return n;
+        } else return kSentinel;
     };
 
 #if TEXIR_CHAIN_PROBE
@@ -523,8 +578,7 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             if (key[1] < inf) { *top = make(code[1], key[1]); top += kBlock; }
             if (key[0] < inf) node = code[0];
             else if constexpr (CULL) {
-                node = kSentinel;
-                while (top != base) { top -= kBlock; const Entry e = *top; if (__int_as_float(e.y) < h.t) { node = e.x; break; } }
+                node = pop_lds();
             }
             else if (top != base) { top -= kBlock; node = *reinterpret_cast<const int*>(top); }
             else node = kSentinel;
@@ -566,6 +620,11 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
     auto leaf_body = [&](auto KZ) __attribute__((always_inline)) {
         constexpr int kzc = decltype(KZ)::value;
         const uint32_t code = ~(uint32_t)node;
+        // the pop that ends the leaf: the two-per-round-trip form unless some lane's stack reaches into the private overflow part (wave-uniform test)
+        auto leaf_pop = [&]() __attribute__((always_inline)) -> int {
+            if constexpr (CULL) { if (!__any(top > lim)) return pop_lds(); }
+            return pop();
+        };
 #if TEXIR_QUAD
         if constexpr (WIDTH == 4) {
             // Quad records (bvh_build.h): three 16-byte words hold the four vertices of two triangles that share the edge (q1, q2): triangle 0 = (q0, q1, q2),
@@ -603,7 +662,7 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
                 // triangle 1 = (A, B, C) = (q3, q2, q1): U = e(q2, q1) = -e(q1, q2), V = e(q1, q3), W = e(q3, q2)
                 accept(-E12, edge2_exact(X1, Y1, X3, Y3), edge2_exact(X3, Y3, X2, Y2), Z3, Z2, Z1, 2 * r + 1);
             }
-            node = pop();
+            node = leaf_pop();
             return;
         }
 #endif
@@ -648,7 +707,7 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
 #endif
             if (ok) { h.t = t; h.u = u; h.v = v; h.slot = i; }
         }
-        node = pop();
+        node = leaf_pop();
     };
     auto leaf_step = [&]() __attribute__((always_inline)) {
 #if TEXIR_TRI_WATERTIGHT && TEXIR_LEAF_UNIFORM_KZ

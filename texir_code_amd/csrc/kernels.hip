@@ -30,12 +30,13 @@ __device__ __forceinline__ uint32_t sample_index(uint32_t pass, uint32_t lane, u
     return (th << (log2N - bth)) | (lane << bphi) | low;
 }
 
-// stats [8] (include/texir_hip.h): rays, node fetches, triangle tests, hits, wave-level node steps, wave-level triangle steps
+// stats [8] (include/texir_hip.h): rays, node fetches, triangle tests, hits, wave-level node steps, wave-level triangle steps, stack entries dropped by
+// culling, pushes + pops through the private overflow part of the stack (wi: trace_core's wave_iters)
 __device__ __forceinline__ void irt_stats_flush(unsigned long long* stats, int lane, uint32_t rays, uint32_t nodes, uint32_t tris,
-                                                uint32_t hits, uint32_t wnodes, uint32_t wtris)
+                                                uint32_t hits, const uint32_t* wi)
 {
-    uint32_t v[6] = {rays, nodes, tris, hits, wnodes, wtris};
-    for (int q = 0; q < 6; q++) {
+    uint32_t v[8] = {rays, nodes, tris, hits, wi[0], wi[1], wi[kWiCulled], wi[kWiOverflow]};
+    for (int q = 0; q < 8; q++) {
         unsigned long long x = v[q];
         for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
         if (lane == 0 && x) atomicAdd(&stats[q], x);
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_kernel(SceneDev sc, c
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t gw = (int64_t)blockIdx.x * (kBlock / 64) + wave, nw = (int64_t)gridDim.x * (kBlock / 64);
-    uint32_t c_nodes = 0, c_tris = 0, c_rays = 0, c_hits = 0, wi[2] = {0, 0};
+    uint32_t c_nodes = 0, c_tris = 0, c_rays = 0, c_hits = 0, wi[kWiSlots] = {0};
     const bool cosw = (mode & kEstimatorCosine) != 0;        // diffuse_reflectance's cosine branch: sum L * pi / N, no n.l factor
     mode &= 3;
     const int passes = (N + 63) >> 6;
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_kernel(SceneDev sc, c
             irr[3 * t + 2] = ((acc2 * two) * pi) / (float)N;
         }
     }
-    if (STATS) irt_stats_flush(stats, lane, c_rays, c_nodes, c_tris, c_hits, wi[0], wi[1]);
+    if (STATS) irt_stats_flush(stats, lane, c_rays, c_nodes, c_tris, c_hits, wi);
 }
 
 // Multi-texel passes.  A wave traces GRP neighbouring texels at once: lane group g (64/GRP lanes) belongs to texel g and all groups
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
     const int lane = threadIdx.x & 63;
     const int grp = lane >> LOG2M, sub = lane & (M - 1);
     const int n_cells = N >> LOG2M;
-    uint32_t cn = 0, ct = 0, c_rays = 0, c_hits = 0, wi[2 + kProbeSlots] = {0};
+    uint32_t cn = 0, ct = 0, c_rays = 0, c_hits = 0, wi[kWiSlots] = {0};
     const bool cosw = (mode & kEstimatorCosine) != 0;
     mode &= 3;
     // A chunk = GRP texels x (all passes / 2^log2parts).  With parts > 1 the raw partial sums go to partial[part][k][3] and
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
         }
 #endif
     }
-    if (STATS) irt_stats_flush(stats, lane, c_rays, cn, ct, c_hits, wi[0], wi[1]);
+    if (STATS) irt_stats_flush(stats, lane, c_rays, cn, ct, c_hits, wi);
 }
 
 // irt_group_kernel with compaction by refill (device_common.h trace_core<STREAM>): same chunks, same hand-out, same per-lane sample order and
@@ -307,7 +308,7 @@ __global__ __launch_bounds__(kBlock, TEXIR_STREAM_WAVES) void irt_stream_kernel(
     constexpr int GRP = 64;
     const int lane = threadIdx.x & 63;
     const int n_cells = N;
-    uint32_t cn = 0, ct = 0, c_rays = 0, c_hits = 0, wi[2] = {0, 0};
+    uint32_t cn = 0, ct = 0, c_rays = 0, c_hits = 0, wi[kWiSlots] = {0};
     const bool cosw = (mode & kEstimatorCosine) != 0;
     mode &= 3;
     const int part_cells = n_cells >> log2parts;
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(kBlock, TEXIR_STREAM_WAVES) void irt_stream_kernel(
             o[0] = acc0; o[1] = acc1; o[2] = acc2;
         }
     }
-    if (STATS) irt_stats_flush(stats, lane, c_rays, cn, ct, c_hits, wi[0], wi[1]);
+    if (STATS) irt_stats_flush(stats, lane, c_rays, cn, ct, c_hits, wi);
 }
 
 __global__ __launch_bounds__(128) void clear_u64_kernel(unsigned long long* __restrict__ p, int n)

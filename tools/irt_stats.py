@@ -22,3 +22,5 @@ print("workload %s: %d texels x %d spp = %d rays, hit rate %.4f" % (wl, ids.nume
 print("per ray : %.2f node fetches, %.2f triangle tests" % (nodes / rays, tris / rays))
 print("per wave-ray: %.2f node steps, %.2f triangle steps" % (wn / wr, wt / wr))
 print("lane utilisation: node step %.3f, triangle step %.3f" % (nodes / (64.0 * wn), tris / (64.0 * max(wt, 1))))
+culled, ovf = int(st[6]), int(st[7])
+print("stack   : %.3f entries dropped by culling per ray (%.1f per wave-ray), %.5f pushes + pops through the private overflow part per ray" % (culled / rays, culled / wr, ovf / rays))
