@@ -431,6 +431,63 @@ TEXIR_API int texir_texel_gbuffer(const texir_scene* scene, int32_t H, int32_t W
                        float* nrm /*dev [H,W,3]*/, uint32_t* prim_id /*dev [H,W], nullable*/, float* bary /*dev [H,W,2], nullable*/,
                        void* workspace /*dev*/, void* stream);
 
+/* ---- the radiance atlas and the index texture from calibrated panoramas (csrc/texbake.hip).  Every stage starts from hdr_texture.hdr and 0.png; the
+ * reference produces neither: its private capture pipeline writes 0.png (per texel: which panorama, at which pixel) and tools/trans_hdr_tex.py:16-61
+ * (repackHDRTexture) only gathers the panoramas' pixels through those codes.  texir_atlas_bake makes the selection: one view and one panorama pixel per
+ * texel, from the mesh (the scene), the texel G-buffer and calibrated panoramas.  The result is a pure function of the inputs.
+ *
+ * THE RULE.  Per texel: pos (ALREADY offset along the normal, as texir_texel_gbuffer delivers it) and nrm (the raw normal, not renormalised).  Per view k:
+ * a 3x4 row-major float32 world-to-camera matrix W_k (rows of cams[k]), the camera position c_k, a panorama [h,w,3] float32 and optionally a validity
+ * mask [h,w] uint8.  The camera frame is the one in which utils/Pano2Cube.py:57-82 measures azimuth and elevation (x right, y up, z front of its front
+ * face; atlas.camera_matrices builds W_k from a final_extrinsics.txt matrix).  With d = c_k - pos, dd = d.d:
+ *   FACING      nrm.d > cos_min sqrt(dd)  and  dd > 0.
+ *   PIXEL       t = W_k (pos, 1);  az = atan2(t.x, t.z);  el = asin(clamp(t.y / |t|, -1, 1));  x = (az / pi + 1) / 2 w;  y = (1 - el / (pi / 2)) / 2 h;
+ *               col = min(floor(x), w - 1), row = min(floor(y), h - 1), both clamped at 0: the pixel Pano2Cube's grid_sample(nearest,
+ *               align_corners=False) reads for that direction, and the pixel tools/trans_hdr_tex.py:50-54 decodes from the code of its centre.
+ *               |t| zero or not finite: no candidate.  With a mask, a pixel whose mask byte is 0 makes the view no candidate.
+ *   VISIBILITY  the ray (org = pos, dir = d): the view is occluded iff its closest hit has t < 1.  Closest hit is what texir_trace_shade reports (Embree
+ *               semantics: t > 0, t in units of |dir|); no extra t_min, because pos is already offset.
+ *   SCORE       s = (nrm.d) / (dd sqrt(dd)): cosine over squared distance.  The winner is the facing, valid, visible view with the largest s; an exact tie
+ *               goes to the lowest view id.
+ *   OUTPUTS     per LISTED texel: view (int32; -1 when no view qualifies), pix = (row, col) (zero when none), rgb = the winner's panorama pixel copied bit
+ *               for bit (zeros when none).  Unlisted texels are untouched.  The pick is nearest, never bilinear: it is what the reference's repack does,
+ *               and an RGBE-born panorama's texels stay RGBE-born (the 4-byte texel layout above stays in force for a baked atlas).
+ *
+ * FLOAT32 OPERATION SEQUENCE (each operation separately rounded, no contraction; sqrt and / correctly rounded; pi32 = 3.14159274, hpi32 = 1.57079637, the
+ * float32 neighbours of pi and pi / 2, off by less than 0.5 u relative):
+ *     d_i = c_i - pos_i;   dd = (d_x d_x + d_y d_y) + d_z d_z;   nd = (n_x d_x + n_y d_y) + n_z d_z;   len = sqrt(dd)
+ *     facing:  dd > 0  and  nd > cos_min * len
+ *     t_i = ((W_i0 pos_x + W_i1 pos_y) + W_i2 pos_z) + W_i3;   r2 = (t_x t_x + t_y t_y) + t_z t_z;   r = sqrt(r2)      (r2 > 0 and finite, else no candidate)
+ *     az = atan2f(t_x, t_z);   q = min(max(t_y / r, -1), 1);   el = asinf(q)
+ *     x = ((az / pi32 + 1) * 0.5) * float(w);   y = ((1 - el / hpi32) * 0.5) * float(h);   col, row = floorf, clamped as floats to [0, w - 1] / [0, h - 1]
+ *     s = nd / (dd * len);   a view replaces the best so far when s > best (views in ascending order)
+ * ROUNDING BOUND (first order, u = 2^-24; the inputs pos, nrm, c, W are exact float32 values; the tests multiply every bound by their factor K):
+ *     |dnd| <= 4 u N1,  N1 = sum_i |n_i d_i|       (d's rounding, three products, two adds)
+ *     |ddd| <= 5 u dd;   |dlen| <= 3.5 u len;   the facing test is decided unless |nd - cos_min len| <= 4 u N1 + 4.5 u |cos_min| len
+ *     |ds|  <= 4 u N1 / (dd len) + 10.5 u |s|      (dd len carries 5 + 3.5 + 1 u; the quotient one more)
+ *     |dt_i| <= 4 u S_i,  S_i = |W_i0 pos_x| + |W_i1 pos_y| + |W_i2 pos_z| + |W_i3|
+ *     |daz| <= (|dt_x| + |dt_z|) / hypot(t_x, t_z) + 12 u |az|          (atan2f taken as accurate to 6 ulp, OpenCL's limit): grows as 1 / hypot(t_x, t_z)
+ *                                                                         towards the poles, where the column is unconstrained
+ *     |dq|  <= |dt_y| / r + |q| ((|t_x| |dt_x| + |t_y| |dt_y| + |t_z| |dt_z|) / r^2 + 2.5 u) + u |q|
+ *     |del| <= min(|dq| / sqrt(1 - (|q| + |dq|)^2), (pi / 2) sqrt(2 |dq|)) + 8 u |el|     (asinf to 4 ulp; asin is Hoelder-1/2 at +-1)
+ *     |dx|  <= w (|daz| / (2 pi) + 3 u);   |dy| <= h (|del| / pi + 3 u)      (pi32's own error, the quotient, the sum, the product with w or h)
+ * A pixel is the rule's pixel unless the exact (x, y) lies within (|dx|, |dy|) of a cell border.
+ *
+ *   pos, nrm [Nt,3] dev;  texel_ids [n_ids] i32 dev, nullable = all Nt texels (n_ids ignored; pass them in Morton order, dist_util.morton_order: a wave is
+ *   64 consecutive ids); an id outside [0, Nt) is skipped.  cams dev [K,12]: W_k rows, then nothing else;  cam_pos dev [K,3];  panos dev [K,h,w,3];
+ *   valid dev [K,h,w] u8, nullable;  K >= 1, h and w in 1..32768;  view [Nt] i32, pix [Nt,2] i32, rgb [Nt,3] f32 dev.
+ *   stats dev u64[4], nullable: += (texel, view) pairs facing, pairs traced, pairs visible, texels assigned.
+ * Caller-owned buffers, the caller's stream, no allocation and no synchronisation: the call records into a hipGraph. */
+TEXIR_API int texir_atlas_bake(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const int32_t* texel_ids /*dev, nullable*/,
+                       int64_t n_ids, int64_t Nt, const float* cams /*dev [K,12]*/, const float* cam_pos /*dev [K,3]*/, const float* panos /*dev [K,h,w,3]*/,
+                       const uint8_t* valid /*dev [K,h,w], nullable*/, int32_t K, int32_t h, int32_t w, float cos_min, int32_t* view /*dev [Nt]*/,
+                       int32_t* pix /*dev [Nt,2]*/, float* rgb /*dev [Nt,3]*/, uint64_t* stats /*dev [4], nullable*/, void* stream);
+/* The device form of the four repack*Texture gathers (tools/trans_hdr_tex.py:16-216: radiance, segmentation ids, albedo / roughness predictions of other
+ * methods; the pixel is utils/Pano2Cube.py:57-82's): out[t, :] = imgs[view[t], pix[t,0], pix[t,1], :] bit for bit for the listed texels, zeros where
+ * view[t] < 0 (or a code points outside the images).  imgs dev [K,h,w,C] f32, C in 1..4; out dev [Nt,C]; texel_ids as above.  Same house rules. */
+TEXIR_API int texir_atlas_gather(const int32_t* view /*dev*/, const int32_t* pix /*dev*/, const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt,
+                       const float* imgs /*dev [K,h,w,C]*/, int32_t K, int32_t h, int32_t w, int32_t C, float* out /*dev [Nt,C]*/, void* stream);
+
 /* ---- host-side codec loops of the file formats around the path (both take HOST pointers) ----------------------------
  * PNG scanline un-filtering (filters 0-4, PNG spec 9.2) of zlib-inflated IDAT data: raw [H][stride+1] -> out [H][stride]; replaces the
  * decode half of cv2.imread("0.png", -1) (models/tracer_o3d_irt.py:91, datasets/dataset.py:489-492). */

@@ -92,6 +92,8 @@ def lib():
         sig["texir_texture_denoise"] = [vp, i32, i32, vp, vp, i32, f32, f32, f32, vp, vp, vp]
         sig["texir_texel_gbuffer_workspace_bytes"] = [vp, i32, i32, C.POINTER(i64)]
         sig["texir_texel_gbuffer"] = [vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp]
+        sig["texir_atlas_bake"] = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
+        sig["texir_atlas_gather"] = [vp, vp, vp, i64, i64, vp, i32, i32, i32, i32, vp, vp]
         sig["texir_png_unfilter"] = [vp, i32, i32, i32, vp]
         L.texir_hdr_decode_scanlines.argtypes = [vp, i64, i32, i32, vp]
         L.texir_hdr_decode_scanlines.restype = i64

@@ -1,0 +1,227 @@
+"""The radiance atlas (hdr_texture.hdr) and the index texture (0.png) of a mesh from calibrated HDR panoramas, on the device.
+
+Every stage starts from those two files; the reference produces neither (its private capture pipeline writes 0.png, tools/trans_hdr_tex.py:16-61 only gathers
+the panoramas' pixels through its codes).  texir_atlas_bake (csrc/texbake.hip; include/texir_hip.h states the rule) picks per texel the view that faces it,
+sees it un-occluded and maximises cosine over squared distance, and the panorama pixel utils/Pano2Cube.py:57-82 reads for the texel's direction.
+
+    python -m texir_code_amd.tools bake-atlas <root> <res|HxW> [--out DIR] [--cos-min X] [--normal geometric|shading] [--seg]
+
+THE CAMERA FRAME.  A final_extrinsics.txt matrix E is camera-to-world with columns (right, column 1, front, position).  cameras.cube_mvps' front face uses
+inverse(E) as it is and puts face row 0 at ndc y = -1, i.e. at NEGATIVE camera y; Pano2Cube's front face has row 0 at sy = +1 and measures
+azimuth = atan2(x, z), elevation = asin(y) (x right, y up, z front).  So Pano2Cube's frame is diag(1, -1, 1) inverse(E): camera_matrices folds the sign of y
+into W.  The other five faces follow from the same frame (cube_mvps' column table and Pano2Cube's rotations agree face by face); tests pin it.
+"""
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+
+CODE_MAX = 50000
+
+
+def camera_matrices(extrinsics):
+    """c2w matrices [K,4,4] (final_extrinsics.txt) -> (W [K,3,4] float32 world -> Pano2Cube camera frame, cam_pos [K,3] float32)"""
+    E = np.asarray(extrinsics, np.float64).reshape(-1, 4, 4)
+    inv = np.linalg.inv(E)
+    S = np.diag([1.0, -1.0, 1.0])
+    W = np.einsum("ij,kjl->kil", S, inv[:, 0:3, :])
+    return torch.from_numpy(np.ascontiguousarray(W, np.float32)), torch.from_numpy(np.ascontiguousarray(E[:, 0:3, 3], np.float32))
+
+
+def pano_xy(W, points):
+    """float64 statement of the pixel rule before the floor: W [3,4], points [...,3] -> (x, y) continuous panorama coordinates in units of w and h
+    (multiply by w, h), i.e. x = (az / pi + 1) / 2, y = (1 - el / (pi / 2)) / 2"""
+    W = torch.as_tensor(W, dtype=torch.float64)
+    p = torch.as_tensor(points, dtype=torch.float64)
+    t = p @ W[:, 0:3].T + W[:, 3]
+    az = torch.atan2(t[..., 0], t[..., 2])
+    el = torch.asin((t[..., 1] / t.norm(dim=-1)).clamp(-1.0, 1.0))
+    return (az / math.pi + 1.0) / 2.0, (1.0 - el / (math.pi / 2.0)) / 2.0
+
+
+def pano_pixel(W, points, h, w):
+    """float64 statement of the pixel rule: W [3,4] (one view of camera_matrices), points [...,3] -> (row, col) int64 of an h x w panorama: the pixel
+    Pano2Cube's grid_sample(nearest, align_corners=False) reads for the point's direction"""
+    x, y = pano_xy(W, points)
+    col = torch.floor(x * w).clamp(0, w - 1).long()
+    row = torch.floor(y * h).clamp(0, h - 1).long()
+    return row, col
+
+
+def _f32(t, dev, shape):
+    return torch.as_tensor(t).to(device=dev, dtype=torch.float32).reshape(*shape).contiguous()
+
+
+def bake_atlas(scene, pos, nrm, W, cam_pos, panos, valid=None, cos_min=0.1, texel_ids=None, out=None, stats=False):
+    """texir_atlas_bake.  pos (already offset), nrm [..,3]; W [K,3,4], cam_pos [K,3] (camera_matrices); panos [K,h,w,3] float32; valid [K,h,w] uint8 or None;
+    texel_ids: int32 list of the texels to decide (None: all; pass dist_util.morton_order's order) -> view [Nt] int32 (-1: no view), pix [Nt,2] int32
+    (row, col), rgb [Nt,3] float32.  Unlisted texels keep what `out` = (view, pix, rgb) held (fresh buffers: view -1, zeros).  stats=True adds a
+    [4] int64 tensor (pairs facing, pairs traced, pairs visible, texels assigned).  Launches on the current stream, no synchronisation."""
+    dev = scene.device
+    pos, nrm = _f32(pos, dev, (-1, 3)), _f32(nrm, dev, (-1, 3))
+    Nt = pos.shape[0]
+    panos = torch.as_tensor(panos).to(device=dev, dtype=torch.float32).contiguous()
+    if panos.ndim != 4 or panos.shape[3] != 3:
+        raise ValueError("bake_atlas: panos must be [K,h,w,3]")
+    K, h, w = int(panos.shape[0]), int(panos.shape[1]), int(panos.shape[2])
+    W, cam_pos = _f32(W, dev, (-1, 12)), _f32(cam_pos, dev, (-1, 3))
+    if W.shape[0] != K or cam_pos.shape[0] != K or nrm.shape[0] != Nt:
+        raise ValueError("bake_atlas: %d panoramas, %d matrices, %d positions; %d pos, %d nrm" % (K, W.shape[0], cam_pos.shape[0], Nt, nrm.shape[0]))
+    if valid is not None:
+        valid = torch.as_tensor(valid).to(device=dev, dtype=torch.uint8).contiguous()
+        if tuple(valid.shape) != (K, h, w):
+            raise ValueError("bake_atlas: valid must be [K,h,w]")
+    if out is None:
+        out = (torch.full((Nt,), -1, device=dev, dtype=torch.int32), torch.zeros((Nt, 2), device=dev, dtype=torch.int32),
+               torch.zeros((Nt, 3), device=dev, dtype=torch.float32))
+    view, pix, rgb = out
+    ids, n_ids = None, 0
+    if texel_ids is not None:
+        ids = texel_ids.to(device=dev, dtype=torch.int32).contiguous()
+        n_ids = ids.numel()
+    st = torch.zeros(4, device=dev, dtype=torch.int64) if stats else None
+    if Nt > 0 and not (texel_ids is not None and n_ids == 0):          # (an empty list must not reach the library: NULL means all texels)
+        _lib.check(_lib.lib().texir_atlas_bake(scene.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(ids), n_ids, Nt, _lib.ptr(W), _lib.ptr(cam_pos), _lib.ptr(panos),
+                                               _lib.ptr(valid), K, h, w, float(cos_min), _lib.ptr(view), _lib.ptr(pix), _lib.ptr(rgb), _lib.ptr(st), _lib.stream_ptr()))
+    return (view, pix, rgb, st) if stats else (view, pix, rgb)
+
+
+def gather_atlas(view, pix, images, texel_ids=None, out=None):
+    """texir_atlas_gather: images [K,h,w,C] (C = 1..4; any dtype, gathered as float32) through (view [Nt], pix [Nt,2]) -> [Nt,C] float32, zeros where
+    view < 0: the device form of the repack*Texture gathers of tools/trans_hdr_tex.py"""
+    dev = view.device
+    img = torch.as_tensor(images).to(device=dev, dtype=torch.float32)
+    if img.ndim == 3:
+        img = img[..., None]
+    img = img.contiguous()
+    K, h, w, C = (int(v) for v in img.shape)
+    view = view.to(torch.int32).reshape(-1).contiguous()
+    Nt = view.shape[0]
+    pix = pix.to(torch.int32).reshape(Nt, 2).contiguous()
+    if out is None:
+        out = torch.zeros((Nt, C), device=dev, dtype=torch.float32)
+    ids, n_ids = None, 0
+    if texel_ids is not None:
+        ids = texel_ids.to(device=dev, dtype=torch.int32).contiguous()
+        n_ids = ids.numel()
+    if Nt > 0 and not (texel_ids is not None and n_ids == 0):
+        _lib.check(_lib.lib().texir_atlas_gather(_lib.ptr(view), _lib.ptr(pix), _lib.ptr(ids), n_ids, Nt, _lib.ptr(img), K, h, w, C, _lib.ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def index_codes(view, pix, h, w):
+    """(view [..], pix [..,2]) -> uint16 [..,3] = (row code, col code, view id): the code of a pixel is round((i + 0.5) / n * 50000) clamped to [1, 50000]
+    (what datasets.write_index_texture_from_panoramas stores; tools/trans_hdr_tex.py:50-53 decodes it back to i); texels without a view are all-zero,
+    the reference's seam"""
+    view = np.asarray(view.cpu() if torch.is_tensor(view) else view).astype(np.int64)
+    pix = np.asarray(pix.cpu() if torch.is_tensor(pix) else pix).astype(np.int64)
+    if view.size and view.max() > 65535:
+        raise ValueError("index_codes: view id %d does not fit 16 bits" % int(view.max()))
+    rc = np.clip(np.rint((pix[..., 0] + 0.5) / h * CODE_MAX), 1, CODE_MAX)
+    cc = np.clip(np.rint((pix[..., 1] + 0.5) / w * CODE_MAX), 1, CODE_MAX)
+    codes = np.stack([rc, cc, np.maximum(view, 0)], -1).astype(np.uint16)
+    codes[view < 0] = 0
+    return codes
+
+
+def decode_codes(codes, h, w):
+    """the inverse, as tools/trans_hdr_tex.py:50-53 decodes: (row, col) = clip(int(code / 50000 * n), 0, n - 1) -> (view [..] int64 (-1: seam), pix [..,2])"""
+    c = np.asarray(codes).astype(np.int64)
+    seam = c.sum(-1) == 0
+    row = np.clip((c[..., 0] / CODE_MAX * h).astype(np.int64), 0, h - 1)
+    col = np.clip((c[..., 1] / CODE_MAX * w).astype(np.int64), 0, w - 1)
+    view = np.where(seam, -1, c[..., 2])
+    pix = np.stack([np.where(seam, 0, row), np.where(seam, 0, col)], -1)
+    return view, pix
+
+
+def pano_directions(W, h, w):
+    """world-space unit directions [h,w,3] (float64) through the pixel CENTRES of one view's h x w panorama: the inverse of the pixel rule"""
+    W = torch.as_tensor(W, dtype=torch.float64)
+    az = ((torch.arange(w, dtype=torch.float64) + 0.5) / w * 2.0 - 1.0) * math.pi
+    el = (1.0 - (torch.arange(h, dtype=torch.float64) + 0.5) / h * 2.0) * (math.pi / 2.0)
+    el, az = torch.meshgrid(el, az, indexing="ij")
+    d = torch.stack([torch.sin(az) * torch.cos(el), torch.sin(el), torch.cos(az) * torch.cos(el)], -1)
+    return d @ torch.linalg.inv(W[:, 0:3]).T
+
+
+def trace_panoramas(scene, c2w, h, w):
+    """the scene's radiance as K equirectangular panoramas [K,h,w,3] (device float32) through scene.trace_shade: one ray per pixel centre from the camera
+    position along the inverse of the pixel rule.  Synthetic input for tests and the timing tool."""
+    W, cam = camera_matrices(c2w)
+    out = []
+    for k in range(W.shape[0]):
+        d = pano_directions(W[k], h, w).to(torch.float32).reshape(-1, 3)
+        o = cam[k].expand_as(d).contiguous()
+        out.append(scene.trace_shade(o, d).reshape(h, w, 3))
+    return torch.stack(out, 0)
+
+
+def read_extrinsics(root):
+    """<root>/info/final_extrinsics.txt -> [K,4,4] float64 (first line is a header, datasets/dataset.py:409)"""
+    with open(os.path.join(root, "info", "final_extrinsics.txt"), "r") as f:
+        lines = [l.replace(" \n", "\n") for l in f.readlines()]
+    return np.loadtxt(lines[1:], delimiter=" ").reshape(-1, 4, 4)
+
+
+def bake_files(root, H, W_atlas, out_dir=None, cos_min=0.1, normal="geometric", seg=False, device=0):
+    """the command: mesh + extrinsics + hdr/<id>/ccm.hdr (+ the alpha of derived/<id>/panoImage_orig.jpg as the mask) -> hdr_texture.hdr, 0.png
+    (+ 0_seg_gray.png) in out_dir.  Returns a dict (paths, the share of covered texels that got a view, the device arrays)."""
+    from . import datasets, dist_util, gbuffer as GB, imgops, io_formats as IO
+    from .scene import Scene
+    mesh_dir = os.path.join(root, "vrproc", "hdr_texture")
+    out_dir = out_dir or os.path.join(mesh_dir, "baked")
+    names = ["hdr_texture.hdr", "0.png"] + (["0_seg_gray.png"] if seg else [])
+    for n in names:
+        if os.path.exists(os.path.join(out_dir, n)):
+            raise FileExistsError("%s exists: bake-atlas does not overwrite" % os.path.join(out_dir, n))
+    with open(os.path.join(root, "info", "aligned.txt"), "r") as f:
+        ids = [l.strip() for l in f.readlines() if l.strip()]
+    E = read_extrinsics(root)
+    if E.shape[0] != len(ids):
+        raise ValueError("%d ids in aligned.txt but %d extrinsics" % (len(ids), E.shape[0]))
+    panos, masks = [], []
+    for i in ids:
+        p = IO.read_hdr(os.path.join(root, "hdr", i, "ccm.hdr"))
+        if panos and p.shape != panos[0].shape:
+            raise ValueError("hdr/%s/ccm.hdr is %s, the first panorama %s" % (i, p.shape, panos[0].shape))
+        panos.append(p)
+        pm = os.path.join(root, "derived", i, "panoImage_orig.jpg")
+        if os.path.exists(pm):
+            rgba = datasets._read_pano_rgba(pm)
+            a = rgba[:, :, 3] if rgba.ndim == 3 and rgba.shape[2] == 4 else np.full(rgba.shape[:2], 255, np.uint8)
+            masks.append(imgops.resize_nearest(np.ascontiguousarray(a), (p.shape[1], p.shape[0])))
+        else:
+            masks.append(None)
+    h, w = panos[0].shape[:2]
+    valid = None
+    if any(m is not None for m in masks):
+        valid = np.stack([np.full((h, w), 255, np.uint8) if m is None else (m > 0).astype(np.uint8) * 255 for m in masks], 0)
+    obj = IO.load_obj(os.path.join(mesh_dir, "out1.obj"))
+    scene = Scene(obj["vertices"], obj["indices"], IO.triangle_uvs_open3d(obj), np.zeros((2, 2, 3), np.float32), device=device)       # (no radiance is read)
+    if normal == "shading":
+        GB.set_corner_normals(scene, IO.corner_normals(obj))
+    pos, nrm, prim, _ = GB.raster_texel_gbuffer(scene, H, W_atlas, normal=normal, want_ids=True)
+    covered = torch.nonzero(prim.reshape(-1) >= 0)[:, 0].to(torch.int32)
+    order = dist_util.morton_order(covered, W_atlas)
+    Wm, cam = camera_matrices(E)
+    view, pix, rgb = bake_atlas(scene, pos, nrm, Wm, cam, np.stack(panos, 0), valid, cos_min, texel_ids=order)
+    os.makedirs(out_dir, exist_ok=True)
+    res = {"dir": out_dir, "view": view, "pix": pix, "rgb": rgb, "covered": int(covered.numel()), "hw": (h, w), "view_count": len(ids)}
+    IO.write_hdr(os.path.join(out_dir, "hdr_texture.hdr"), rgb.reshape(H, W_atlas, 3).cpu().numpy())     # file orientation, no exposure
+    codes = index_codes(view, pix, h, w).reshape(H, W_atlas, 3)
+    IO.write_png(os.path.join(out_dir, "0.png"), np.ascontiguousarray(codes[..., ::-1]))                  # the file stores RGB = (view id, col code, row code)
+    if seg:
+        segs = []
+        for i in ids:
+            s = IO.read_png(os.path.join(root, "derived", i, "panoImage_gray.png"))
+            s = s[..., 0] if s.ndim == 3 else s
+            segs.append(imgops.resize_nearest(np.ascontiguousarray(s), (w, h)))
+        g = gather_atlas(view, pix, np.stack(segs, 0).astype(np.float32)).reshape(H, W_atlas)
+        IO.write_png(os.path.join(out_dir, "0_seg_gray.png"), g.cpu().numpy().astype(np.uint8))
+    n_view = int((view.reshape(-1)[covered.long()] >= 0).sum().item())
+    res["share"] = n_view / max(1, res["covered"])
+    return res

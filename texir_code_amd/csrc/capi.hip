@@ -668,4 +668,37 @@ int texir_texel_gbuffer(const texir_scene* s, int32_t H, int32_t W, int32_t norm
     return TEXIR_OK;
 }
 
+/* ---- the radiance atlas + index texture from calibrated panoramas, csrc/texbake.hip.  The reference has no producer of either file: its private capture
+ * pipeline writes 0.png and tools/trans_hdr_tex.py:16-61 (repackHDRTexture) only gathers the panoramas' pixels through those codes; the panorama pixel of
+ * a direction is the one utils/Pano2Cube.py:57-82 reads (grid_sample nearest, align_corners=False). ---- */
+int texir_atlas_bake(const texir_scene* s, const float* pos, const float* nrm, const int32_t* texel_ids, int64_t n_ids, int64_t Nt, const float* cams,
+                     const float* cam_pos, const float* panos, const uint8_t* valid, int32_t K, int32_t h, int32_t w, float cos_min, int32_t* view, int32_t* pix,
+                     float* rgb, uint64_t* stats, void* stream)
+{
+    if (!s || !pos || !nrm || !cams || !cam_pos || !panos) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: null argument (scene, pos, nrm, cams, cam_pos and panos are required)");
+    if (!view || !pix || !rgb) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: null output (view, pix and rgb are required)");
+    if (K < 1) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: K must be >= 1 (got %d)", K);
+    if (h < 1 || w < 1 || h > 32768 || w > 32768) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: h and w must be 1..32768 (got %d x %d)", h, w);
+    if (Nt < 0 || (texel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: negative texel count");
+    if (!(cos_min - cos_min == 0.0f)) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: cos_min must be finite");
+    HIP_TRY(launch_atlas_bake(dev_of(s), pos, nrm, texel_ids, texel_ids ? n_ids : Nt, Nt, cams, cam_pos, panos, valid, K, h, w, cos_min, view, pix, rgb,
+                              (unsigned long long*)stats, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
+/* the gathers of tools/trans_hdr_tex.py:16-216 (repackHDRTexture, repackSegTexture, repackAlbedoTexture, repackRoughnessTexture: pixel (row, col) of
+ * panorama `view`, utils/Pano2Cube.py:57-82's pixel) through the (view, pix) texir_atlas_bake wrote */
+int texir_atlas_gather(const int32_t* view, const int32_t* pix, const int32_t* texel_ids, int64_t n_ids, int64_t Nt, const float* imgs, int32_t K, int32_t h,
+                       int32_t w, int32_t C, float* out, void* stream)
+{
+    if (!view || !pix || !imgs) return fail(TEXIR_ERR_INVALID, "texir_atlas_gather: null argument (view, pix and imgs are required)");
+    if (!out) return fail(TEXIR_ERR_INVALID, "texir_atlas_gather: null output");
+    if (K < 1) return fail(TEXIR_ERR_INVALID, "texir_atlas_gather: K must be >= 1 (got %d)", K);
+    if (h < 1 || w < 1 || h > 32768 || w > 32768) return fail(TEXIR_ERR_INVALID, "texir_atlas_gather: h and w must be 1..32768 (got %d x %d)", h, w);
+    if (C < 1 || C > 4) return fail(TEXIR_ERR_INVALID, "texir_atlas_gather: C must be 1..4 (got %d)", C);
+    if (Nt < 0 || (texel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "texir_atlas_gather: negative texel count");
+    HIP_TRY(launch_atlas_gather(view, pix, texel_ids, texel_ids ? n_ids : Nt, Nt, imgs, K, h, w, C, out, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 }  // extern "C"

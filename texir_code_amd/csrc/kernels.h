@@ -65,4 +65,10 @@ hipError_t launch_texture_denoise(const float* img, int H, int W, const float* n
 size_t texel_raster_workspace_bytes(int64_t n_slots, int64_t T, int H, int W);
 hipError_t launch_texel_raster(const SceneDev& sc, const float4* cnrm /*nullable unless shading*/, int64_t n_slots, int64_t T, int H, int W, int shading, float offset,
                                float* pos, float* nrm, uint32_t* prim_id /*nullable*/, float* bary /*nullable*/, void* workspace, hipStream_t st);
+// texbake.hip: the radiance atlas and the index texture from calibrated panoramas (tools/trans_hdr_tex.py:16-61 gathers through the codes this selects)
+hipError_t launch_atlas_bake(const SceneDev& sc, const float* pos, const float* nrm, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt, const float* cams,
+                             const float* cam_pos, const float* panos, const uint8_t* valid /*nullable*/, int K, int h, int w, float cos_min, int32_t* view, int32_t* pix,
+                             float* rgb, unsigned long long* stats /*nullable*/, hipStream_t st);
+hipError_t launch_atlas_gather(const int32_t* view, const int32_t* pix, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt, const float* imgs, int K, int h,
+                               int w, int C, float* out, hipStream_t st);
 }  // namespace texir

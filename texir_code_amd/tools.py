@@ -21,6 +21,13 @@ Without --gpu: this module's CPU path (mode reference; --mode nearest needs --gp
 
 The texel G-buffer of any uv-mapped mesh (position + 1e-2 * normal, normal; zero on the texels no triangle covers), rasterised in uv space on the
 device (gbuffer.raster_texel_gbuffer) and written in the format train.texel_gbuffer = file reads.  <res> is the atlas size, or HxW.
+
+    python -m texir_code_amd.tools bake-atlas <root> <res|HxW> [--out DIR] [--cos-min X] [--normal geometric|shading] [--seg]
+
+The radiance atlas hdr_texture.hdr and the index texture 0.png of <root>/vrproc/hdr_texture/out1.obj from the calibrated panoramas hdr/<id>/ccm.hdr
+(info/aligned.txt, info/final_extrinsics.txt; the alpha of derived/<id>/panoImage_orig.jpg masks invalid pixels when it exists), selected per texel on the
+device (atlas.bake_atlas, csrc/texbake.hip), written into DIR (default <root>/vrproc/hdr_texture/baked; existing files are not overwritten).  --seg adds
+0_seg_gray.png gathered from derived/<id>/panoImage_gray.png.
 """
 import sys
 
@@ -104,8 +111,16 @@ def write_texel_gbuffer(path_obj, H, W, dst, normal="geometric", device=0):
 
 def main(argv):
     flags, rest, mode, normal = [], [], None, "geometric"
+    out_dir, cos_min = None, "0.1"
     it = iter(argv)
     for a in it:
+        if a in ("--out", "--cos-min") or a.startswith("--out=") or a.startswith("--cos-min="):
+            key, val = a.split("=", 1) if "=" in a else (a, next(it, None))
+            if key == "--out":
+                out_dir = val
+            else:
+                cos_min = val
+            continue
         if a == "--mode":
             mode = next(it, None)
         elif a.startswith("--mode="):
@@ -132,6 +147,26 @@ def main(argv):
         dst = argv[3] if len(argv) > 3 else argv[1].replace("out1.obj", "texel_gbuffer.npz") if "out1.obj" in argv[1] else "texel_gbuffer.npz"
         n = write_texel_gbuffer(argv[1], H, W, dst, normal)
         print("wrote %s (%d x %d, %d texels covered)" % (dst, H, W, n))
+        return 0
+    if len(argv) >= 3 and argv[0] == "bake-atlas":
+        from . import atlas
+        try:
+            hw = [int(v) for v in argv[2].lower().split("x")]
+            H, W = (hw[0], hw[0]) if len(hw) == 1 else hw
+            cm = float(cos_min)
+        except (ValueError, TypeError):
+            print("<res> must be an integer or HxW and --cos-min a number, got %r, %r" % (argv[2], cos_min))
+            return 2
+        if normal not in ("geometric", "shading"):
+            print("--normal must be geometric or shading")
+            return 2
+        try:
+            res = atlas.bake_files(argv[1], H, W, out_dir, cm, normal, "--seg" in flags)
+        except FileExistsError as e:
+            print(e)
+            return 1
+        print("wrote %s (%d x %d from %d panoramas of %d x %d): %.2f %% of %d covered texels got a view"
+              % (res["dir"], H, W, res["view_count"], res["hw"][0], res["hw"][1], 100.0 * res["share"], res["covered"]))
         return 0
     if len(argv) < 2 or argv[0] != "pad":
         print(__doc__)
