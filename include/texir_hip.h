@@ -488,6 +488,53 @@ TEXIR_API int texir_atlas_bake(const texir_scene* scene, const float* pos /*dev*
 TEXIR_API int texir_atlas_gather(const int32_t* view /*dev*/, const int32_t* pix /*dev*/, const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt,
                        const float* imgs /*dev [K,h,w,C]*/, int32_t K, int32_t h, int32_t w, int32_t C, float* out /*dev [Nt,C]*/, void* stream);
 
+/* ---- the fill of the texels the bake left unobserved (csrc/texfill.hip; no reference counterpart: the reference's capture pipeline delivers a complete
+ * atlas).  A covered texel no panorama sees gets view = -1 and zeros from texir_atlas_bake; texir_texture_pad would fill it from its nearest neighbour IN UV
+ * SPACE, which may be an unrelated chart.  texir_atlas_fill names, per hole, the nearest OBSERVED texel IN WORLD SPACE whose normal agrees with the hole's:
+ * a hidden piece of floor continues the visible floor around it.  The caller copies the radiance (rgb[hole] = rgb[src[hole]]).
+ *
+ * THE RULE.  pos, nrm [Nt,3] float32: the texel G-buffer as texir_atlas_bake takes it (pos already offset, nrm raw, not renormalised).  source_ids: the
+ * observed texels; hole_ids: the texels to decide; cos_fill in [0, 1]; max_dist > 0 (+inf allowed).  For hole t and source s, with e = pos[s] - pos[t],
+ * nt = nrm[t], ns_ = nrm[s]:
+ *   WITHIN      |e|^2 <= max_dist^2
+ *   COMPATIBLE  nt.ns_ > 0  and  (nt.ns_)^2 >= cos_fill^2 |nt|^2 |ns_|^2      (the cosine test without a square root; a zero normal is compatible with
+ *               nothing, because nt.ns_ > 0 fails)
+ *   WINNER      the within, compatible source with the smallest |e|^2; an exact float32 tie goes to the lowest texel id
+ *   OUTPUT      per LISTED hole: src[t] = the winner's texel id, or -1; dist2[t] = its dd (0 when none).  Unlisted texels are untouched.
+ * The result is a pure function of the inputs: the order of either list, duplicates in them, the launch shape, `bounds`, the search structure and its cell
+ * size do not change a bit.  An id outside [0, Nt) is skipped, in either list.  A texel in both lists is its own source (dd = 0) when its normal is not zero.
+ *
+ * FLOAT32 OPERATION SEQUENCE (each operation separately rounded, no contraction; only IEEE subtractions, products, sums and comparisons occur, so a
+ * float32 restatement on any IEEE machine gives the same bits):
+ *     e_i = pos[s]_i - pos[t]_i;   dd = (e_x e_x + e_y e_y) + e_z e_z
+ *     ns = (nt_x ns_x + nt_y ns_y) + nt_z ns_z;   nn_t = (nt_x nt_x + nt_y nt_y) + nt_z nt_z;   nn_s likewise
+ *     r2 = max_dist * max_dist;   c2 = cos_fill * cos_fill
+ *     within:  dd <= r2;   compatible:  ns > 0  and  ns * ns >= (c2 * nn_t) * nn_s
+ *     s replaces the best so far when dd < best, or dd == best and s < best's id
+ * ROUNDING BOUND (first order, u = 2^-24; the inputs are exact float32 values; the tests multiply every bound by their factor K):
+ *     |d dd| <= 5 u dd                              (e_i: one rounding, its square two more and one; the first sum one, the second one: (1 + u)^5 on the
+ *                                                    x and y terms, (1 + u)^4 on z; every term is non-negative)
+ *     |d ns| <= 3 u N1,  N1 = sum_i |nt_i ns_i|     (a product, two sums);   |d nn| <= 3 u nn  likewise
+ *     the compatibility test is decided unless |ns^2 - c^2 nn_t nn_s| <= 6 u N1 |ns| + u ns^2 + 9 u c^2 nn_t nn_s
+ *                                                   (2 |ns| |d ns| and the square's own rounding; c2 one, nn_t three, their product one, nn_s three, the
+ *                                                    last product one)
+ *     the range test is decided unless |dd - r2| <= 5 u dd + u r2
+ *
+ *   bounds: HOST float[6] = (min x, y, z, max x, y, z), finite: a box around the listed positions over which the sources are binned.  It steers speed only,
+ *   never the result: positions outside it are searched through the border cells, slower and still exact.   cell: the edge of a grid cell, 0 = the
+ *   library chooses (texir_atlas_fill_cell reports the edge a call will use: a given edge is doubled until the grid fits the workspace).
+ *   src dev [Nt] i32;  dist2 dev [Nt] f32, nullable;  stats dev u64[2], nullable: += list entries decided (valid hole ids, a duplicate counts again), and
+ *   those of them that were filled.  n_src == 0 is no error: every hole gets -1.  Pass the holes in Morton order (dist_util.morton_order): a wave owns 64
+ *   consecutive holes and searches the cells around their common box.
+ *   workspace: texir_atlas_fill_workspace_bytes(n_src, n_holes) bytes of device scratch, 16-byte aligned.
+ * Caller-owned buffers, the caller's stream, no allocation and no synchronisation: the call records into a hipGraph. */
+TEXIR_API int64_t texir_atlas_fill_workspace_bytes(int64_t n_src, int64_t n_holes);
+TEXIR_API float texir_atlas_fill_cell(const float* bounds /*host [6]*/, int64_t n_src, float cell);
+TEXIR_API int texir_atlas_fill(const float* pos /*dev*/, const float* nrm /*dev*/, int64_t Nt, const int32_t* source_ids /*dev*/, int64_t n_src,
+                       const int32_t* hole_ids /*dev*/, int64_t n_holes, const float* bounds /*host [6]*/, float cos_fill, float max_dist, float cell,
+                       int32_t* src /*dev [Nt]*/, float* dist2 /*dev [Nt], nullable*/, uint64_t* stats /*dev [2], nullable*/, void* workspace /*dev*/,
+                       void* stream);
+
 /* ---- host-side codec loops of the file formats around the path (both take HOST pointers) ----------------------------
  * PNG scanline un-filtering (filters 0-4, PNG spec 9.2) of zlib-inflated IDAT data: raw [H][stride+1] -> out [H][stride]; replaces the
  * decode half of cv2.imread("0.png", -1) (models/tracer_o3d_irt.py:91, datasets/dataset.py:489-492). */

@@ -1,0 +1,167 @@
+"""No GPU: the float32 restatement of the atlas fill's rule (atlas_fill_cases.fill_f32) states the rule of include/texir_hip.h -- its pick is admissible under
+the float64 reference with the header's bounds for every hole of every case -- the checker rejects seven mutants, the reference is sharp on the room (at most
+3 % of the holes have more than one admissible outcome), and the pieces around the kernel (declarations, ctypes signatures, the command's parser, the gutter
+dilation's index logic) are in place.
+
+Figures from the reference alone, room64_bake (1 825 sources, 1 227 holes, cos_fill 0.5): 14 holes (1.1 %) with more than one admissible outcome at max_dist
+0.5, 16 (1.3 %) at 1.0.  On lattice_tie every hole ties exactly between two or four sources and the tie rule leaves one admissible outcome each.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import atlas_fill_cases as C
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("name", C.ALL)
+def test_float32_restatement_is_admissible(name):
+    case = C.case(name)
+    src, dist2, stats = C.fill_f32(case, sentinel=C.SENTINEL)
+    fails = C.check(case, src, dist2, sentinel=C.SENTINEL)
+    print(name, case.ref().stats(), stats.tolist())
+    assert not fails, (len(fails), fails[:5])
+    H = case.valid_holes()
+    assert stats[0] >= len(H) and stats[1] <= stats[0] and (len(np.unique(case.holes)) < len(case.holes) or stats[1] == int((src[H] >= 0).sum()))
+
+
+def test_case_sizes():
+    a, b = C.case("room64_bake"), C.case("room96_balls")
+    assert (len(a.valid_sources()), len(a.valid_holes())) == (1825, 1227)
+    assert (len(b.valid_sources()), len(b.valid_holes())) == (6426, 478)
+    for h in C.LIST_HOLES:
+        for s in C.LIST_SOURCES:
+            c = C.case("list_h%d_s%d" % (h, s))
+            assert (len(c.holes), len(c.sources)) == (h, s)
+    d = C.case("dup_oor")
+    assert len(np.unique(d.holes)) < len(d.holes) and (d.holes < 0).any() and (d.sources >= d.Nt).any() and np.intersect1d(d.sources, d.holes).size >= 4
+    e = C.case("bounds_exclude")
+    ids = np.concatenate([e.valid_sources(), e.valid_holes()])
+    out = (e.pos[ids, 0] > e.bounds[3]).mean()
+    assert 0.3 < out < 0.37, out
+
+
+def test_named_outcomes():
+    """the cases whose outcome the construction fixes"""
+    src = C.case("edge_of_range").f32()[0]
+    assert src[:4].tolist() == [4, -1, 6, -1]                              # dd == r2: within; one ulp above: out; ns ns == (c2 nn_t) nn_s: compatible; beyond: not
+    assert (C.case("no_sources").f32()[0][C.case("no_sources").valid_holes()] == -1).all()
+    c = C.case("all_incompatible")
+    assert (c.f32()[0][c.valid_holes()] == -1).all() and c.ref().none_ok.all() and not c.ref().ok.any()
+    # lattice_tie: every hole has two or four sources at its smallest distance, and the lowest id among them wins
+    c = C.case("lattice_tie")
+    src, dist2, _ = c.f32()
+    S = c.valid_sources()
+    for t in c.valid_holes():
+        d = ((c.pos[S].astype(np.float64) - c.pos[t].astype(np.float64)) ** 2).sum(1)
+        near = S[d == d.min()]
+        assert len(near) in (2, 4) and src[t] == near.min() and dist2[t] == np.float32(d.min())
+    # a texel in both lists is its own source
+    d = C.case("dup_oor")
+    both = np.intersect1d(d.valid_sources(), d.valid_holes())
+    assert len(both) >= 4 and (d.f32()[0][both] == both).all() and (d.f32()[1][both] == 0).all()
+    # max_dist = +inf: a hole stays empty only when NO source is compatible
+    i = C.case("inf_dist")
+    assert (i.f32()[0][i.valid_holes()] >= 0).sum() > (C.case("room64_far").f32()[0][i.valid_holes()] >= 0).sum()
+
+
+@pytest.mark.parametrize("mut", C.MUTANTS)
+def test_checker_rejects_mutant(mut):
+    case = C.case(C.MUTANT_CASES[mut])
+    src, dist2, _ = C.fill_f32(case, mut)
+    fails = C.check(case, src, dist2)
+    print(mut, len(fails), fails[:1])
+    assert fails
+
+
+def test_raw_normals_pick_as_unit_normals():
+    """normals of length 0.3 .. 3 (and the same zero normals): the picks are admissible under the reference of the unit-normal case, i.e. the same except
+    where the bound leaves a choice"""
+    raw, unit = C.case("raw_normals"), C.case("raw_normals_unit")
+    assert np.array_equal(raw.nrm == 0, unit.nrm == 0) and (raw.nrm == 0).all(1).sum() > 100
+    src, dist2, _ = raw.f32()
+    fails = C.check(unit, src, dist2)
+    assert not fails, (len(fails), fails[:5])
+    H = raw.valid_holes()
+    same = (src[H] == unit.f32()[0][H]).mean()
+    print("raw against unit normals: %.4f of %d holes pick the same source" % (same, len(H)))
+    assert same >= 1.0 - C.CAP_MULTI
+    zero = H[(raw.nrm[H] == 0).all(1)]
+    assert len(zero) and (src[zero] == -1).all()                          # a zero normal is compatible with nothing
+
+
+@pytest.mark.parametrize("name", ["room64_bake", "room64_far"])
+def test_cap_on_the_room(name):
+    """from the reference alone: at most 3 % (atlas_bake_cases.CAP_MULTI, the bake's own cap) of the holes have more than one admissible outcome"""
+    ref = C.case(name).ref()
+    print(name, ref.stats(), "%.4f" % ref.caps())
+    assert C.CAP_MULTI == 0.03 and ref.caps() <= C.CAP_MULTI, ref.stats()
+
+
+def test_header_and_signatures():
+    hdr = open(os.path.join(ROOT, "include", "texir_hip.h")).read()
+    for fn in ("texir_atlas_fill", "texir_atlas_fill_workspace_bytes"):
+        assert re.search(r"TEXIR_API\s+\w+\s+%s\(" % fn, hdr), fn
+    # the bounds the reference uses are the header's
+    for text in ("|d dd| <= 5 u dd", "|d ns| <= 3 u N1", "|d nn| <= 3 u nn", "6 u N1 |ns| + u ns^2 + 9 u c^2 nn_t nn_s", "|dd - r2| <= 5 u dd + u r2"):
+        assert text in hdr, text
+    lib_py = open(os.path.join(ROOT, "texir_code_amd", "_lib.py")).read()
+    assert 'sig["texir_atlas_fill"]' in lib_py and "texir_atlas_fill_workspace_bytes.argtypes" in lib_py
+    from texir_code_amd import _lib
+    L = _lib.lib()
+    assert len(L.texir_atlas_fill.argtypes) == 16 and L.texir_atlas_fill_workspace_bytes.restype is not None
+    # the workspace grows with the sources and never shrinks below the grid's own arrays
+    w0, w1 = L.texir_atlas_fill_workspace_bytes(0, 10), L.texir_atlas_fill_workspace_bytes(100000, 10)
+    assert w0 > 0 and w1 >= w0 + 32 * 100000 - 64
+
+
+def test_parser_accepts_the_fill_options():
+    from texir_code_amd import tools
+    o = tools.parse_bake_atlas(["root", "64x32", "--fill", "--fill-dist", "0.25", "--fill-cos=0.75", "--seg"])
+    assert o["fill"] and o["seg"] and (o["H"], o["W"]) == (64, 32) and o["fill_dist"] == 0.25 and o["fill_cos"] == 0.75
+    o = tools.parse_bake_atlas(["root", "64"])
+    assert not o["fill"] and o["fill_dist"] == 0.5 and o["fill_cos"] == 0.5 and o["cos_min"] == 0.1 and o["normal"] == "geometric"
+    for bad in (["--fill-dist", "-1"], ["--fill-dist", "0"], ["--fill-cos", "1.5"], ["--fill-cos", "-0.1"], ["--fill-dist", "far"], ["--fill-cos", "nan"]):
+        with pytest.raises(ValueError):
+            tools.parse_bake_atlas(["root", "64", "--fill"] + bad)
+        assert tools.main(["bake-atlas", "root", "64", "--fill"] + bad) == 2
+
+
+def test_dilate_gutters_index_logic():
+    """which texels may change, on a hand-made 6 x 8 coverage map, the pad's src stubbed by brute force (nearest covered texel in uv space, itself for a
+    covered texel): exactly the uncovered texels change, each reads a covered texel at minimal distance, covered texels (black ones included) never do"""
+    from texir_code_amd import atlas
+    cov = np.array([[0, 0, 0, 0, 0, 0, 0, 0],
+                    [0, 1, 1, 0, 0, 0, 0, 0],
+                    [0, 1, 1, 0, 0, 1, 1, 0],
+                    [0, 0, 0, 0, 0, 1, 1, 0],
+                    [0, 0, 0, 0, 0, 0, 1, 0],
+                    [0, 0, 0, 0, 0, 0, 0, 0]], bool)
+    H, W = cov.shape
+    rr, cc = np.nonzero(cov)
+    src = np.zeros((H, W), np.int64)
+    d2min = np.zeros((H, W), np.int64)
+    for r in range(H):
+        for c_ in range(W):
+            d2 = (rr - r) ** 2 + (cc - c_) ** 2
+            j = int(d2.argmin())
+            src[r, c_], d2min[r, c_] = rr[j] * W + cc[j], d2[j]
+    t, s = atlas.gutter_targets(cov, src)
+    assert np.array_equal(np.sort(t), np.nonzero(~cov.reshape(-1))[0])
+    assert cov.reshape(-1)[s].all()
+    assert np.array_equal(((s // W - t // W) ** 2 + (s % W - t % W) ** 2), d2min.reshape(-1)[t])
+    # a pad that found nothing (-1 everywhere) changes nothing; a source that is itself uncovered is not read
+    t, s = atlas.gutter_targets(cov, np.full((H, W), -1))
+    assert len(t) == 0
+    bad = src.copy()
+    bad[0, 0] = 7                                                          # texel (0, 7) is uncovered
+    t, s = atlas.gutter_targets(cov, bad)
+    assert 0 not in t.tolist() and cov.reshape(-1)[s].all()
+    # the same on torch tensors
+    import torch
+    t2, s2 = atlas.gutter_targets(torch.from_numpy(cov), torch.from_numpy(src.astype(np.int32)))
+    t, s = atlas.gutter_targets(cov, src)
+    assert np.array_equal(t2.numpy(), t) and np.array_equal(s2.numpy(), s)

@@ -94,6 +94,11 @@ def lib():
         sig["texir_texel_gbuffer"] = [vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp]
         sig["texir_atlas_bake"] = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
         sig["texir_atlas_gather"] = [vp, vp, vp, i64, i64, vp, i32, i32, i32, i32, vp, vp]
+        L.texir_atlas_fill_workspace_bytes.argtypes = [i64, i64]
+        L.texir_atlas_fill_workspace_bytes.restype = i64
+        L.texir_atlas_fill_cell.argtypes = [vp, i64, f32]
+        L.texir_atlas_fill_cell.restype = f32
+        sig["texir_atlas_fill"] = [vp, vp, i64, vp, i64, vp, i64, vp, f32, f32, f32, vp, vp, vp, vp, vp]
         sig["texir_png_unfilter"] = [vp, i32, i32, i32, vp]
         L.texir_hdr_decode_scanlines.argtypes = [vp, i64, i32, i32, vp]
         L.texir_hdr_decode_scanlines.restype = i64

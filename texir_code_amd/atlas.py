@@ -5,6 +5,10 @@ the panoramas' pixels through its codes).  texir_atlas_bake (csrc/texbake.hip; i
 sees it un-occluded and maximises cosine over squared distance, and the panorama pixel utils/Pano2Cube.py:57-82 reads for the texel's direction.
 
     python -m texir_code_amd.tools bake-atlas <root> <res|HxW> [--out DIR] [--cos-min X] [--normal geometric|shading] [--seg]
+                                              [--fill] [--fill-dist D] [--fill-cos C]
+
+--fill completes what the bake leaves: texir_atlas_fill (csrc/texfill.hip) names, per covered texel no panorama sees, the nearest OBSERVED texel in world
+space whose normal agrees (fill_atlas), and dilate_gutters gives the texels outside every chart their uv-nearest covered texel.
 
 THE CAMERA FRAME.  A final_extrinsics.txt matrix E is camera-to-world with columns (right, column 1, front, position).  cameras.cube_mvps' front face uses
 inverse(E) as it is and puts face row 0 at ndc y = -1, i.e. at NEGATIVE camera y; Pano2Cube's front face has row 0 at sy = +1 and measures
@@ -112,6 +116,103 @@ def gather_atlas(view, pix, images, texel_ids=None, out=None):
     return out
 
 
+def scene_bounds(vertices, offset=1e-2):
+    """host vertices [V,3] -> float32 [6] = (min, max) grown by the G-buffer's offset: the box fill_atlas bins its sources over"""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    return np.concatenate([v.min(0) - offset, v.max(0) + offset]).astype(np.float32)
+
+
+def _fill_bounds(bounds, pos, lists):
+    if bounds is not None:
+        b = np.ascontiguousarray(np.asarray(bounds, np.float32).reshape(6))
+        if not np.isfinite(b).all() or (b[3:] < b[:3]).any():
+            raise ValueError("fill_atlas: bounds must be six finite numbers (min xyz, max xyz), got %s" % b.tolist())
+        return b
+    ids = torch.cat([l.reshape(-1).long() for l in lists])
+    ids = ids[(ids >= 0) & (ids < pos.shape[0])]
+    if ids.numel() == 0:
+        return np.array([0, 0, 0, 1, 1, 1], np.float32)
+    p = pos[ids]
+    p = torch.where(torch.isfinite(p), p, torch.zeros_like(p))
+    return torch.cat([p.min(0).values, p.max(0).values]).cpu().numpy().astype(np.float32)
+
+
+def fill_cell(bounds, n_src, cell=0.0):
+    """the grid cell edge texir_atlas_fill searches with for these arguments (cell = 0: the library's choice)"""
+    b = np.ascontiguousarray(np.asarray(bounds, np.float32).reshape(6))
+    return float(_lib.lib().texir_atlas_fill_cell(_lib.ptr(b), int(n_src), float(cell)))
+
+
+def fill_atlas(pos, nrm, source_ids, hole_ids, cos_fill=0.5, max_dist=0.5, bounds=None, out=None, stats=False, dist2=False, cell=0.0):
+    """texir_atlas_fill.  pos (already offset), nrm [..,3] device float32 (the G-buffer bake_atlas took); source_ids: the observed texels, hole_ids: the
+    texels to decide (int32 lists; pass the holes in dist_util.morton_order's order) -> src [Nt] int32: per listed hole the nearest source in world space
+    within max_dist whose normal agrees (cosine >= cos_fill), lowest id on an exact tie, or -1.  Unlisted texels keep what `out` = src or (src, dist2) held
+    (a fresh src is -1 everywhere, a fresh dist2 zero).  dist2=True adds the float32 squared distances [Nt], stats=True a [2] int64 tensor (holes decided,
+    holes filled).  bounds: six host numbers (scene_bounds: the scene's vertices grown by the offset) that steer speed only; None takes the listed
+    positions' own box from the device, which costs one device-to-host copy -- pass bounds to launch on the current stream with no synchronisation.
+    cell: the grid's cell edge, 0 = the library chooses (fill_cell reports it)."""
+    if not torch.is_tensor(pos) or not pos.is_cuda:
+        raise _lib.TexirError("fill_atlas: pos must be a device tensor")
+    dev = pos.device
+    pos, nrm = _f32(pos, dev, (-1, 3)), _f32(nrm, dev, (-1, 3))
+    Nt = pos.shape[0]
+    if nrm.shape[0] != Nt:
+        raise ValueError("fill_atlas: %d pos, %d nrm" % (Nt, nrm.shape[0]))
+    if not (0.0 <= float(cos_fill) <= 1.0) or not float(max_dist) > 0.0:
+        raise ValueError("fill_atlas: cos_fill must be in [0, 1] and max_dist > 0 (got %r, %r)" % (cos_fill, max_dist))
+    sid = torch.as_tensor(source_ids).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    hid = torch.as_tensor(hole_ids).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    b = _fill_bounds(bounds, pos, (sid, hid))
+    src, d2 = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
+    if src is None:
+        src = torch.full((Nt,), -1, device=dev, dtype=torch.int32)
+    if dist2 and d2 is None:
+        d2 = torch.zeros((Nt,), device=dev, dtype=torch.float32)
+    st = torch.zeros(2, device=dev, dtype=torch.int64) if stats else None
+    L = _lib.lib()
+    if hid.numel() > 0:
+        ws = torch.empty(max(16, int(L.texir_atlas_fill_workspace_bytes(sid.numel(), hid.numel()))), device=dev, dtype=torch.uint8)
+        _lib.check(L.texir_atlas_fill(_lib.ptr(pos), _lib.ptr(nrm), Nt, _lib.ptr(sid) if sid.numel() else None, sid.numel(), _lib.ptr(hid), hid.numel(),
+                                      _lib.ptr(b), float(cos_fill), float(max_dist), float(cell), _lib.ptr(src), _lib.ptr(d2), _lib.ptr(st), _lib.ptr(ws),
+                                      _lib.stream_ptr()))
+    res = (src,) + ((d2,) if dist2 else ()) + ((st,) if stats else ())
+    return res if len(res) > 1 else src
+
+
+def gutter_targets(covered, src):
+    """the index logic of dilate_gutters on host or device arrays: covered [H,W] bool, src [H,W] = the pad's source index per texel -> (flat ids of the
+    texels that change, flat ids they read): the UNCOVERED texels whose source is a covered texel; covered texels never change"""
+    xp = torch if torch.is_tensor(covered) else np
+    c = covered.reshape(-1) != 0
+    s = src.reshape(-1)
+    if xp is torch:
+        s = s.long()
+        ok = ~c & (s >= 0)
+        ok = ok & c[s.clamp(min=0)]
+        t = torch.nonzero(ok)[:, 0]
+    else:
+        s = s.astype(np.int64)
+        ok = ~c & (s >= 0)
+        ok = ok & c[np.clip(s, 0, None)]
+        t = np.nonzero(ok)[0]
+    return t, s[t]
+
+
+def dilate_gutters(image, covered):
+    """image [H,W,C] (device), covered [H,W] bool -> a copy in which every UNCOVERED texel holds the value of the nearest covered texel in uv space
+    (texir_texture_pad on a one-channel coverage image, then a gather of `image` through its sources); covered texels are never touched, those left black
+    on purpose included.  With no covered texel at all the copy equals the image."""
+    from . import texpost
+    H, W = covered.shape
+    cov = covered.to(device=image.device).reshape(H, W)
+    _, src = texpost.pad_texture(cov.to(torch.float32)[..., None].contiguous(), mode="nearest", return_src=True)
+    t, s = gutter_targets(cov, src)
+    out = image.clone()
+    flat = out.reshape(H * W, -1)
+    flat[t] = image.reshape(H * W, -1)[s]
+    return out
+
+
 def index_codes(view, pix, h, w):
     """(view [..], pix [..,2]) -> uint16 [..,3] = (row code, col code, view id): the code of a pixel is round((i + 0.5) / n * 50000) clamped to [1, 50000]
     (what datasets.write_index_texture_from_panoramas stores; tools/trans_hdr_tex.py:50-53 decodes it back to i); texels without a view are all-zero,
@@ -167,14 +268,25 @@ def read_extrinsics(root):
     return np.loadtxt(lines[1:], delimiter=" ").reshape(-1, 4, 4)
 
 
-def bake_files(root, H, W_atlas, out_dir=None, cos_min=0.1, normal="geometric", seg=False, device=0):
+def _packs_exactly(rgb):
+    """every texel is three 8-bit integers times one power of two (texir_texel_pack): the condition of the scene's 4-byte texel layout"""
+    a = np.ascontiguousarray(rgb.detach().cpu().numpy().reshape(-1, 3), np.float32)
+    ok = np.zeros(len(a), np.uint8)
+    _lib.check(_lib.lib().texir_texel_pack(_lib.ptr(a), len(a), _lib.ptr(np.zeros(len(a), np.uint32)), _lib.ptr(ok)))
+    return bool(ok.all())
+
+
+def bake_files(root, H, W_atlas, out_dir=None, cos_min=0.1, normal="geometric", seg=False, device=0, fill=False, fill_dist=0.5, fill_cos=0.5):
     """the command: mesh + extrinsics + hdr/<id>/ccm.hdr (+ the alpha of derived/<id>/panoImage_orig.jpg as the mask) -> hdr_texture.hdr, 0.png
-    (+ 0_seg_gray.png) in out_dir.  Returns a dict (paths, the share of covered texels that got a view, the device arrays)."""
+    (+ 0_seg_gray.png) in out_dir.  Returns a dict (paths, the share of covered texels that got a view, the device arrays).
+    fill=True completes the atlas before it is written: unobserved covered texels from the nearest compatible observed texel in world space (fill_atlas,
+    fill_dist scene units, cosine fill_cos), then the texels outside every chart from their uv-nearest covered texel (dilate_gutters); 0.png keeps the
+    observed texels' codes only; atlas_fill.npz holds the sources; the dict gains fill_src and the counts observed, filled, black (covered texels)."""
     from . import datasets, dist_util, gbuffer as GB, imgops, io_formats as IO
     from .scene import Scene
     mesh_dir = os.path.join(root, "vrproc", "hdr_texture")
     out_dir = out_dir or os.path.join(mesh_dir, "baked")
-    names = ["hdr_texture.hdr", "0.png"] + (["0_seg_gray.png"] if seg else [])
+    names = ["hdr_texture.hdr", "0.png"] + (["0_seg_gray.png"] if seg else []) + (["atlas_fill.npz"] if fill else [])
     for n in names:
         if os.path.exists(os.path.join(out_dir, n)):
             raise FileExistsError("%s exists: bake-atlas does not overwrite" % os.path.join(out_dir, n))
@@ -211,6 +323,22 @@ def bake_files(root, H, W_atlas, out_dir=None, cos_min=0.1, normal="geometric", 
     view, pix, rgb = bake_atlas(scene, pos, nrm, Wm, cam, np.stack(panos, 0), valid, cos_min, texel_ids=order)
     os.makedirs(out_dir, exist_ok=True)
     res = {"dir": out_dir, "view": view, "pix": pix, "rgb": rgb, "covered": int(covered.numel()), "hw": (h, w), "view_count": len(ids)}
+    fill_src = filled_ids = None
+    if fill:
+        seen = view[order.long()] >= 0
+        sources, holes = order[seen].contiguous(), order[~seen].contiguous()                  # both keep the Morton order
+        fill_src = fill_atlas(pos, nrm, sources, holes, fill_cos, fill_dist, bounds=scene_bounds(obj["vertices"]))
+        filled_ids = holes[fill_src[holes.long()] >= 0].long()
+        born = _packs_exactly(rgb)
+        rgb[filled_ids] = rgb[fill_src[filled_ids].long()]                                    # the source's bits as they are
+        cov = torch.zeros(H * W_atlas, dtype=torch.bool, device=rgb.device)
+        cov[covered.long()] = True
+        rgb = dilate_gutters(rgb.reshape(H, W_atlas, 3), cov.reshape(H, W_atlas)).reshape(-1, 3)
+        # the 4-byte texel layout (Scene.texture_layout() >= 3) is chosen when every texel packs exactly; the fill only copies texels, so it stays in force
+        assert not born or _packs_exactly(rgb), "the fill copies texels: an RGBE-born atlas must stay RGBE-born"
+        np.savez(os.path.join(out_dir, "atlas_fill.npz"), src=fill_src.reshape(H, W_atlas).cpu().numpy())
+        res.update(rgb=rgb, fill_src=fill_src, observed=int(sources.numel()), filled=int(filled_ids.numel()),
+                   black=int(holes.numel() - filled_ids.numel()))
     IO.write_hdr(os.path.join(out_dir, "hdr_texture.hdr"), rgb.reshape(H, W_atlas, 3).cpu().numpy())     # file orientation, no exposure
     codes = index_codes(view, pix, h, w).reshape(H, W_atlas, 3)
     IO.write_png(os.path.join(out_dir, "0.png"), np.ascontiguousarray(codes[..., ::-1]))                  # the file stores RGB = (view id, col code, row code)
@@ -220,7 +348,10 @@ def bake_files(root, H, W_atlas, out_dir=None, cos_min=0.1, normal="geometric", 
             s = IO.read_png(os.path.join(root, "derived", i, "panoImage_gray.png"))
             s = s[..., 0] if s.ndim == 3 else s
             segs.append(imgops.resize_nearest(np.ascontiguousarray(s), (w, h)))
-        g = gather_atlas(view, pix, np.stack(segs, 0).astype(np.float32)).reshape(H, W_atlas)
+        g = gather_atlas(view, pix, np.stack(segs, 0).astype(np.float32))
+        if fill:
+            g[filled_ids] = g[fill_src[filled_ids].long()]                                    # a filled texel takes its source's class; gutters stay 0
+        g = g.reshape(H, W_atlas)
         IO.write_png(os.path.join(out_dir, "0_seg_gray.png"), g.cpu().numpy().astype(np.uint8))
     n_view = int((view.reshape(-1)[covered.long()] >= 0).sum().item())
     res["share"] = n_view / max(1, res["covered"])

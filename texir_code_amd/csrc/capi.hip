@@ -701,4 +701,42 @@ int texir_atlas_gather(const int32_t* view, const int32_t* pix, const int32_t* t
     return TEXIR_OK;
 }
 
+/* ---- the fill of the texels the bake left unobserved, csrc/texfill.hip: nearest compatible observed texel in world space (no reference counterpart) ---- */
+int64_t texir_atlas_fill_workspace_bytes(int64_t n_src, int64_t n_holes)
+{
+    if (n_src < 0 || n_holes < 0) return 0;
+    return (int64_t)atlas_fill_workspace_bytes(n_src, n_holes);
+}
+
+static bool fill_bounds_ok(const float* b)
+{
+    if (!b) return false;
+    for (int i = 0; i < 6; i++)
+        if (!(b[i] - b[i] == 0.0f)) return false;
+    return b[3] >= b[0] && b[4] >= b[1] && b[5] >= b[2];
+}
+
+float texir_atlas_fill_cell(const float* bounds, int64_t n_src, float cell)
+{
+    if (!fill_bounds_ok(bounds) || n_src < 0) return 0.0f;
+    return atlas_fill_cell(bounds, n_src, cell);
+}
+
+int texir_atlas_fill(const float* pos, const float* nrm, int64_t Nt, const int32_t* source_ids, int64_t n_src, const int32_t* hole_ids, int64_t n_holes,
+                     const float* bounds, float cos_fill, float max_dist, float cell, int32_t* src, float* dist2, uint64_t* stats, void* workspace, void* stream)
+{
+    if (!pos || !nrm || !src || !workspace) return fail(TEXIR_ERR_INVALID, "texir_atlas_fill: null argument (pos, nrm, src and workspace are required)");
+    if (Nt < 0 || n_src < 0 || n_holes < 0) return fail(TEXIR_ERR_INVALID, "texir_atlas_fill: negative count");
+    if ((n_src > 0 && !source_ids) || (n_holes > 0 && !hole_ids)) return fail(TEXIR_ERR_INVALID, "texir_atlas_fill: null id list");
+    if (n_src > 0xFFFFFFFFll) return fail(TEXIR_ERR_INVALID, "texir_atlas_fill: n_src must fit 32 bits");
+    if (!fill_bounds_ok(bounds)) return fail(TEXIR_ERR_INVALID, "texir_atlas_fill: bounds must be six finite floats (min x y z, max x y z) with max >= min");
+    if (!(cos_fill >= 0.0f && cos_fill <= 1.0f)) return fail(TEXIR_ERR_INVALID, "texir_atlas_fill: cos_fill must be in [0, 1] (got %g)", (double)cos_fill);
+    if (!(max_dist > 0.0f)) return fail(TEXIR_ERR_INVALID, "texir_atlas_fill: max_dist must be > 0 (+inf allowed; got %g)", (double)max_dist);
+    if (!(cell >= 0.0f) || !(cell - cell == 0.0f)) return fail(TEXIR_ERR_INVALID, "texir_atlas_fill: cell must be finite and >= 0 (0: the library chooses)");
+    if (((uintptr_t)workspace & 15) != 0) return fail(TEXIR_ERR_INVALID, "texir_atlas_fill: workspace must be 16-byte aligned");
+    HIP_TRY(launch_atlas_fill(pos, nrm, Nt, source_ids, n_src, hole_ids, n_holes, bounds, cos_fill, max_dist, cell, src, dist2, (unsigned long long*)stats,
+                              workspace, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 }  // extern "C"

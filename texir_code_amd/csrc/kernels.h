@@ -71,4 +71,11 @@ hipError_t launch_atlas_bake(const SceneDev& sc, const float* pos, const float* 
                              float* rgb, unsigned long long* stats /*nullable*/, hipStream_t st);
 hipError_t launch_atlas_gather(const int32_t* view, const int32_t* pix, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt, const float* imgs, int K, int h,
                                int w, int C, float* out, hipStream_t st);
+// texfill.hip: unobserved texels of a baked atlas from the nearest observed texel in world space whose normal agrees (exact grid search)
+int64_t atlas_fill_cell_cap(int64_t n_src);
+size_t atlas_fill_workspace_bytes(int64_t n_src, int64_t n_holes);
+float atlas_fill_cell(const float bounds[6], int64_t n_src, float cell);        // the cell edge a call with these arguments searches with
+hipError_t launch_atlas_fill(const float* pos, const float* nrm, int64_t Nt, const int32_t* source_ids, int64_t n_src, const int32_t* hole_ids, int64_t n_holes,
+                             const float bounds[6] /*host*/, float cos_fill, float max_dist, float cell, int32_t* src, float* dist2 /*nullable*/,
+                             unsigned long long* stats /*nullable*/, void* workspace, hipStream_t st);
 }  // namespace texir

@@ -23,11 +23,21 @@ The texel G-buffer of any uv-mapped mesh (position + 1e-2 * normal, normal; zero
 device (gbuffer.raster_texel_gbuffer) and written in the format train.texel_gbuffer = file reads.  <res> is the atlas size, or HxW.
 
     python -m texir_code_amd.tools bake-atlas <root> <res|HxW> [--out DIR] [--cos-min X] [--normal geometric|shading] [--seg]
+                                              [--fill] [--fill-dist D] [--fill-cos C]
 
 The radiance atlas hdr_texture.hdr and the index texture 0.png of <root>/vrproc/hdr_texture/out1.obj from the calibrated panoramas hdr/<id>/ccm.hdr
 (info/aligned.txt, info/final_extrinsics.txt; the alpha of derived/<id>/panoImage_orig.jpg masks invalid pixels when it exists), selected per texel on the
 device (atlas.bake_atlas, csrc/texbake.hip), written into DIR (default <root>/vrproc/hdr_texture/baked; existing files are not overwritten).  --seg adds
 0_seg_gray.png gathered from derived/<id>/panoImage_gray.png.
+
+--fill completes the atlas (atlas.fill_atlas, csrc/texfill.hip): a covered texel no panorama sees takes the radiance of the nearest OBSERVED texel in world
+space within D scene units (--fill-dist, default 0.5: the depth of what stands on an indoor floor -- a choice, not a measurement) whose normal agrees with
+its own to a cosine of C (--fill-cos, default 0.5); where nothing compatible is near it stays black.  Then the texels outside every chart take their
+uv-nearest covered texel (atlas.dilate_gutters), so that bilinear footprints along chart borders read no black.  0.png keeps codes for OBSERVED texels only:
+a filled texel is not seen by the view it borrows from, and under the `pano` G-buffer route its code would put it at the source's position; with
+train.texel_gbuffer = raster the IrT stage computes irradiance at filled texels too.  atlas_fill.npz (src int32 [H,W], -1 elsewhere, file orientation) is
+written beside the atlas so that later gathers can be completed the same way; with --seg a filled texel takes its source's class and gutters stay 0.
+Without --fill every file is what the command wrote before the option existed, bit for bit.
 """
 import sys
 
@@ -109,7 +119,62 @@ def write_texel_gbuffer(path_obj, H, W, dst, normal="geometric", device=0):
     return int((prim >= 0).sum().item())
 
 
+def parse_bake_atlas(argv):
+    """the arguments after `bake-atlas` -> dict(root, H, W, out, cos_min, normal, seg, fill, fill_dist, fill_cos); ValueError names what is wrong"""
+    opt = {"--out": None, "--cos-min": "0.1", "--normal": "geometric", "--fill-dist": "0.5", "--fill-cos": "0.5"}
+    flags, rest = [], []
+    it = iter(argv)
+    for a in it:
+        key = a.split("=", 1)[0]
+        if key in opt:
+            opt[key] = a.split("=", 1)[1] if "=" in a else next(it, None)
+        elif a.startswith("--"):
+            flags.append(a)
+        else:
+            rest.append(a)
+    if len(rest) < 2:
+        raise ValueError("bake-atlas needs <root> and <res|HxW>")
+    try:
+        hw = [int(v) for v in rest[1].lower().split("x")]
+        H, W = (hw[0], hw[0]) if len(hw) == 1 else hw
+        cm = float(opt["--cos-min"])
+    except (ValueError, TypeError):
+        raise ValueError("<res> must be an integer or HxW and --cos-min a number, got %r, %r" % (rest[1], opt["--cos-min"]))
+    if opt["--normal"] not in ("geometric", "shading"):
+        raise ValueError("--normal must be geometric or shading")
+    try:
+        fd, fc = float(opt["--fill-dist"]), float(opt["--fill-cos"])
+    except (ValueError, TypeError):
+        raise ValueError("--fill-dist and --fill-cos must be numbers, got %r, %r" % (opt["--fill-dist"], opt["--fill-cos"]))
+    if not fd > 0.0:
+        raise ValueError("--fill-dist must be > 0, got %r" % fd)
+    if not 0.0 <= fc <= 1.0:
+        raise ValueError("--fill-cos must be in [0, 1], got %r" % fc)
+    return {"root": rest[0], "H": H, "W": W, "out": opt["--out"], "cos_min": cm, "normal": opt["--normal"], "seg": "--seg" in flags, "fill": "--fill" in flags,
+            "fill_dist": fd, "fill_cos": fc}
+
+
 def main(argv):
+    if len(argv) >= 3 and argv[0] == "bake-atlas":
+        from . import atlas
+        try:
+            o = parse_bake_atlas(argv[1:])
+        except ValueError as e:
+            print(e)
+            return 2
+        try:
+            res = atlas.bake_files(o["root"], o["H"], o["W"], o["out"], o["cos_min"], o["normal"], o["seg"], fill=o["fill"], fill_dist=o["fill_dist"],
+                                   fill_cos=o["fill_cos"])
+        except FileExistsError as e:
+            print(e)
+            return 1
+        print("wrote %s (%d x %d from %d panoramas of %d x %d): %.2f %% of %d covered texels got a view"
+              % (res["dir"], o["H"], o["W"], res["view_count"], res["hw"][0], res["hw"][1], 100.0 * res["share"], res["covered"]))
+        if o["fill"]:
+            n = max(1, res["covered"])
+            print("fill (dist %g, cos %g): %.2f %% of the covered texels observed, %.2f %% filled, %.2f %% left black"
+                  % (o["fill_dist"], o["fill_cos"], 100.0 * res["observed"] / n, 100.0 * res["filled"] / n, 100.0 * res["black"] / n))
+        return 0
     flags, rest, mode, normal = [], [], None, "geometric"
     out_dir, cos_min = None, "0.1"
     it = iter(argv)
@@ -147,26 +212,6 @@ def main(argv):
         dst = argv[3] if len(argv) > 3 else argv[1].replace("out1.obj", "texel_gbuffer.npz") if "out1.obj" in argv[1] else "texel_gbuffer.npz"
         n = write_texel_gbuffer(argv[1], H, W, dst, normal)
         print("wrote %s (%d x %d, %d texels covered)" % (dst, H, W, n))
-        return 0
-    if len(argv) >= 3 and argv[0] == "bake-atlas":
-        from . import atlas
-        try:
-            hw = [int(v) for v in argv[2].lower().split("x")]
-            H, W = (hw[0], hw[0]) if len(hw) == 1 else hw
-            cm = float(cos_min)
-        except (ValueError, TypeError):
-            print("<res> must be an integer or HxW and --cos-min a number, got %r, %r" % (argv[2], cos_min))
-            return 2
-        if normal not in ("geometric", "shading"):
-            print("--normal must be geometric or shading")
-            return 2
-        try:
-            res = atlas.bake_files(argv[1], H, W, out_dir, cm, normal, "--seg" in flags)
-        except FileExistsError as e:
-            print(e)
-            return 1
-        print("wrote %s (%d x %d from %d panoramas of %d x %d): %.2f %% of %d covered texels got a view"
-              % (res["dir"], H, W, res["view_count"], res["hw"][0], res["hw"][1], 100.0 * res["share"], res["covered"]))
         return 0
     if len(argv) < 2 or argv[0] != "pad":
         print(__doc__)

@@ -1,12 +1,15 @@
-"""Time of the atlas bake (texir_atlas_bake, csrc/texbake.hip) on one GPU.
+"""Time of the atlas bake (texir_atlas_bake, csrc/texbake.hip) and of the fill of what it leaves (texir_atlas_fill, csrc/texfill.hip) on one GPU.
 
-    python tools/atlas_bake_time.py [--workload c4] [--views 16] [--pano 1024x2048] [--out profiles/atlas_bake.json]
+    python tools/atlas_bake_time.py [--workload c4] [--views 16] [--pano 1024x2048] [--fill] [--fill-dist 0.5] [--fill-cos 0.5] [--out profiles/atlas_bake.json]
 
 The scene of bench.py's workload (c4: 1M triangles, 4096^2 atlas), its texel G-buffer from the device rasteriser (gbuffer.raster_texel_gbuffer), --views
 cameras on cameras.grid_cameras' grid, their panoramas from atlas.trace_panoramas, the covered texels in Morton order.  Recorded: the HIP-event median of
 texir_atlas_bake (20 timed launches after 3 warm-up launches; launches only, every buffer made once), its `stats` counters and the rays per second they
 imply, and, for scale, the texir_trace_shade ray rate on the panoramas' own rays measured in the same process.  No parent route computes the same thing:
-the time is a recorded figure, not a threshold.  There is no CPU fallback: without a GPU this fails."""
+the time is a recorded figure, not a threshold.  --fill adds texir_atlas_fill on the holes this bake leaves (sources: the covered texels with a view, holes:
+those without, both in Morton order; the box of the scene's vertices grown by the G-buffer offset): the HIP-event median of the whole call (binning + search;
+the same launch counts, or 1 + 5 when one call takes longer than two seconds), its `stats` counters and the cell edge the library chose.
+There is no CPU fallback: without a GPU this fails."""
 import argparse
 import json
 import math
@@ -20,13 +23,13 @@ sys.path.insert(0, ROOT)
 WARMUP, REPEATS = 3, 20
 
 
-def gpu_ms(fn):
+def gpu_ms(fn, warmup=WARMUP, repeats=REPEATS):
     import torch
-    for _ in range(WARMUP):
+    for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
     ts = []
-    for _ in range(REPEATS):
+    for _ in range(repeats):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         fn()
@@ -41,6 +44,9 @@ def main():
     ap.add_argument("--workload", default="c4")
     ap.add_argument("--views", type=int, default=16)
     ap.add_argument("--pano", default="1024x2048")
+    ap.add_argument("--fill", action="store_true")
+    ap.add_argument("--fill-dist", type=float, default=0.5)
+    ap.add_argument("--fill-cos", type=float, default=0.5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "atlas_bake.json"))
     a = ap.parse_args()
     import numpy as np
@@ -90,6 +96,28 @@ def main():
     ts["rays"] = int(d.shape[0])
     ts["rays_per_s"] = round(d.shape[0] / (ts["median_ms"] * 1e-3), 1)
     out["trace_shade_panorama"] = ts
+    if a.fill:
+        import time
+        seen = view[ids.long()] >= 0
+        sources, holes = ids[seen].contiguous(), ids[~seen].contiguous()
+        bounds = atlas.scene_bounds(sc0["verts"])
+        src = torch.full((Nt,), -1, dtype=torch.int32, device="cuda")
+        fst = torch.zeros(2, dtype=torch.int64, device="cuda")
+        ws = torch.empty(int(L.texir_atlas_fill_workspace_bytes(sources.numel(), holes.numel())), dtype=torch.uint8, device="cuda")
+
+        def fill(stats=None):
+            _lib.check(L.texir_atlas_fill(p(pos), p(nrm), Nt, p(sources), sources.numel(), p(holes), holes.numel(), p(bounds), a.fill_cos, a.fill_dist, 0.0, p(src), None,
+                                          p(stats), p(ws), _lib.stream_ptr()))
+        t0 = time.time()
+        fill(fst)
+        torch.cuda.synchronize()
+        first_s = time.time() - t0
+        wu, rp = (1, 5) if first_s > 2.0 else (WARMUP, REPEATS)
+        fc = dict(zip(("holes_decided", "holes_filled"), (int(v) for v in fst.cpu())))
+        out["atlas_fill"] = gpu_ms(fill, wu, rp)
+        out["atlas_fill"].update({"warmup": wu, "repeats": rp, "sources": int(sources.numel()), "holes": int(holes.numel()), "fill_dist": a.fill_dist,
+                                  "fill_cos": a.fill_cos, "cell": round(atlas.fill_cell(bounds, sources.numel()), 6), "bounds": [round(float(v), 4) for v in bounds],
+                                  "workspace_bytes": int(ws.numel()), "stats": fc})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
