@@ -141,6 +141,37 @@ TEXIR_API int texir_irt_generate(const texir_scene* scene, const float* pos /*de
  * unaffected.  No reference counterpart. */
 TEXIR_API int texir_scene_reserve_scratch(texir_scene* scene, int64_t n_ids, int32_t N);
 
+/* ---- irradiance split by source label (csrc/irtsplit.hip): where a texel's irradiance comes from, K classes in ONE traced pass.  Irradiance is linear in
+ * the radiance texture, so the share class k's texels contribute -- the lamps, the floor, a window -- gives every recolouring, dimming or switching off
+ * of that class as a weighted sum (the reference re-traces the diffuse term per view and per colour instead: models/test_nvdiffrast.py:268-274).
+ *
+ * THE RULE.  Inputs: everything texir_irt_generate takes; labels dev uint8 [Ht,Wt] in the orientation of the texture the scene holds (labels[y][x] is
+ * the class of the texel the hit shader reads at row y, column x); K in 1..8; the flag `unit`.
+ *   SAMPLES AND RAYS  directions, n.l, the ray, the acceptance test (slot >= 0 && t > 1e-4) and the closest hit are exactly those of
+ *               irt_group_kernel<false, 4, 6>, texir_irt_generate's 64-texel form: one texel per lane, one sample per pass.
+ *   SHADING     for a hit, x0, y0, x1, y1, w00, w10, w01, w11 are computed exactly as the hit shader computes them (bilinear / border /
+ *               align_corners=False).  For class k and channel c, separately rounded float32 operations in this order:
+ *                   L_k[c] = v00 w00;  L_k[c] += v10 w10;  L_k[c] += v01 w01;  L_k[c] += v11 w11
+ *               v_ab = value(tap ab)[c] if labels[y_b][x_a] == k, else +0.0f.  With `unit`, value is 1.0f in all channels and the texture is not read.
+ *               A label >= K belongs to no class.  This is the float32 expression the hit shader evaluates on a texture whose other-class texels are +0.
+ *   REDUCTION   the documented 64-texel plan whatever the list length: acc_k += L_k ndl per lane over the passes of a part, in irt_group_kernel's pass
+ *               order (azimuthal wedges); the parts are those of the 64-texel form -- a power-of-two N is cut into up to 32 parts of at least
+ *               TEXIR_IRT_MIN_PART_CELLS (8) passes, capped by TEXIR_IRT_LOG2PARTS; any other N is one part in natural sample order -- and are added in
+ *               part order; out[k][t][c] = ((a * 2) * pi) / N, as texir_irt_generate writes it.
+ *   CONSEQUENCE out[k] is, bit for bit, what texir_irt_generate in its 64-texel form (TEXIR_IRT_TEXELS_PER_WAVE=64, or any list of >= 32 768 texels)
+ *               writes for the same scene with the texture tex * [label == k]: the rays are the same, the products are the same, and adding +0 changes
+ *               no float.  With `unit`, out[k] is what it writes for the indicator texture of class k.
+ * The result is a pure function of the inputs: list order, list cuts, launch shape and stream do not change a bit.
+ *   out [K][Nt][3] dev: only listed texels are written.  texel_ids NULL => all Nt (n_ids ignored); a non-null list with n_ids == 0 is a no-op.
+ *   workspace: texir_irt_split_workspace_bytes(n_ids, N, K) bytes of device scratch (12 bytes x K x parts per listed texel: callers cut long lists into
+ *   slices that are multiples of 64 texels -- scene.Scene.irt_split does; 0 is returned for arguments the call refuses).
+ * Caller-owned buffers, the caller's stream, no allocation and no synchronisation: the call records into a hipGraph.  K outside 1..8, null labels,
+ * N < 1, a workspace that is too small and a scene without the 4-wide tree (TEXIR_BVH_WIDTH=2) are errors with a texir_last_error() text. */
+TEXIR_API int64_t texir_irt_split_workspace_bytes(int64_t n_ids, int32_t N, int32_t K);
+TEXIR_API int texir_irt_split(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const float* shift /*dev*/,
+                       const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode, const uint8_t* labels /*dev [Ht,Wt]*/,
+                       int32_t K, int32_t unit, float* out /*dev [K][Nt][3]*/, void* workspace /*dev*/, int64_t workspace_bytes, void* stream);
+
 /* name of the kernel form ONE texir_irt_generate call over n_ids listed texels at N samples launches on this scene
  * ("irt_group_kernel<false, 4, 6>": 64 texels per wave; "irt_kernel<false, 4|2>": one texel per wave) -- the launcher's own
  * decision, so that bench.py's roofline names the kernel that really ran.  buf receives a NUL-terminated string. */

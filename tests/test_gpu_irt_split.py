@@ -1,0 +1,285 @@
+"""irt_split_kernel / irt_split_combine_kernel (csrc/irtsplit.hip) behind texir_irt_split, Scene.irt_split, the IrT stage's train.irt_split and the
+relight-irt command, on the golden room (20 k triangles, 256^2 texture, a lamp).
+
+  1. intervals   every class of `lamp` and `bands` inside the float64 reference of its masked texture (irt_split_cases.split_ref);
+  2. equality    bit for bit the existing 64-texel kernel on the masked (unit: indicator) textures: N in 1, 64, 65, 100, 128, 512 and once 2048, every label
+                 image, lists of 130 / 64 / 65 / 1 texels, float-valued (layout 2) and RGBE-born (layout 4) textures;
+  3. linearity   combine(E, c) against irt_generate on the recoloured texture, relative L2 <= 1e-3 (the project's parity bound);
+  4. purity      shuffled list, three slices, second run, side stream, a captured graph replayed twice: identical bits; sentinels and guard words intact;
+  5. errors      every refused argument raises TexirError;
+  6. stage       train.irt_split = lights writes the class files; their sum is the plain file within RGBE quantisation; relight-irt round-trips.
+"""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import irt_split_cases as SP
+import trace_cases as TC
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = 7.0
+_SC = {}
+
+
+def world(tx, kind):
+    """(scene holding the full texture, scene whose texture the masked runs replace, the full texture) -- kind 'float' | 'born'"""
+    if kind not in _SC:
+        from texir_code_amd import synth
+        geo, _ = TC.golden_geo(SP.SCENE)
+        hdr = geo.hdr if kind == "float" else synth.rgbe_born(geo.hdr)
+        full, mask = tx.Scene(geo.verts, geo.tris, geo.tri_uvs, hdr), tx.Scene(geo.verts, geo.tris, geo.tri_uvs, hdr)
+        assert full.texture_layout() == (2 if kind == "float" else 4)
+        _SC[kind] = (full, mask, np.ascontiguousarray(hdr, np.float32))
+    return _SC[kind]
+
+
+_DEV = {}
+
+
+def texel_inputs():
+    if not _DEV:
+        c = TC.irt_case(SP.SCENE, 130, 64, "uniform")
+        _DEV["v"] = tuple(torch.from_numpy(a).cuda() for a in (c.pos, c.nrm, c.shift))
+    return _DEV["v"]
+
+
+def ids_of(n):
+    return torch.from_numpy(TC.listed(SP.SCENE, n).astype(np.int32)).cuda()
+
+
+def split(sc, lab, K, N, ids, unit=False, **kw):
+    pos, nrm, shift = texel_inputs()
+    out = torch.full((K, pos.shape[0], 3), SENTINEL, device="cuda")
+    got = sc.irt_split(pos, nrm, shift, N, torch.from_numpy(lab), K, texel_ids=ids, unit=unit, out=out, **kw)
+    assert got is out
+    return out.cpu().numpy()
+
+
+def generate(sc, N, ids):
+    pos, nrm, shift = texel_inputs()
+    out = torch.full((pos.shape[0], 3), SENTINEL, device="cuda")
+    return sc.irt_generate(pos, nrm, shift, N, "uniform", texel_ids=ids, out=out).cpu().numpy()
+
+
+# ---- 1. intervals ------------------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name,n_tex,N", SP.REF_CASES, ids=["%s_%dx%d" % c for c in SP.REF_CASES])
+def test_every_class_inside_the_float64_reference_of_its_masked_texture(tx, name, n_tex, N):
+    K, lab = SP.labels(name)
+    full, _, _ = world(tx, "float")
+    use = TC.listed(SP.SCENE, n_tex)
+    got = split(full, lab, K, N, ids_of(n_tex))
+    parts = TC.n_parts(N, "group")
+    for k in range(K):
+        worst = SP.split_ref(name, k, n_tex, N).check(got[k][use], "group", parts, "irt_split", "%s class %d %dx%d" % (name, k, n_tex, N))
+        print("irt_split %s class %d %dx%d: worst share of the interval %.3f" % (name, k, n_tex, N, worst))
+    unlisted = np.ones(got.shape[1], bool)
+    unlisted[use] = False
+    assert (got[:, unlisted] == SENTINEL).all()
+
+
+# ---- 2. equality with the existing kernel ----------------------------------------------------------------------------------------------------------------------
+
+def equal_to_masked_runs(tx, monkeypatch, kind, name, unit, Ns, lists):
+    monkeypatch.setenv("TEXIR_IRT_TEXELS_PER_WAVE", "64")
+    K, lab = SP.labels(name)
+    full, mask, hdr = world(tx, kind)
+    ids = {n: ids_of(n) for n in lists}
+    got = {(N, n): split(full, lab, K, N, ids[n], unit=unit) for N in Ns for n in lists}
+    for k in range(K):
+        mask.set_texture(SP.masked_hdr(lab, k, hdr, unit=unit))
+        for N in Ns:
+            for n in lists:
+                assert mask.irt_kernel_name(n, N) == "irt_group_kernel<false, 4, 6>"
+                want = generate(mask, N, ids[n])
+                g = got[(N, n)][k]
+                if not np.array_equal(g, want):
+                    bad = np.argwhere(g != want)
+                    raise AssertionError("%s %s class %d N=%d list=%d unit=%s: %d values differ; first at %s: split %r, masked run %r"
+                                         % (kind, name, k, N, n, unit, len(bad), bad[0], float(g[tuple(bad[0])]), float(want[tuple(bad[0])])))
+    return got
+
+
+@pytest.mark.parametrize("name", SP.LABEL_NAMES)
+@pytest.mark.parametrize("kind", ["float", "born"])
+def test_split_equals_the_64_texel_kernel_on_the_masked_textures(tx, monkeypatch, kind, name):
+    got = equal_to_masked_runs(tx, monkeypatch, kind, name, False, SP.N_EQUAL, SP.LISTS)
+    full, _, _ = world(tx, kind)
+    if name == "zeros":
+        # one class that owns every texel: the plain irt_generate, bit for bit
+        for (N, n), g in got.items():
+            assert np.array_equal(g[0], generate(full, N, ids_of(n))), (N, n)
+    if name == "dropped":
+        # a label >= K belongs to no class: classes 0 and 1 of `bands`
+        K3, bands = SP.labels("bands")
+        for (N, n), g in got.items():
+            assert np.array_equal(g, split(full, bands, K3, N, ids_of(n))[:2]), (N, n)
+
+
+@pytest.mark.parametrize("name", SP.LABEL_NAMES)
+def test_unit_split_equals_the_64_texel_kernel_on_the_indicator_textures(tx, monkeypatch, name):
+    equal_to_masked_runs(tx, monkeypatch, "float", name, True, SP.N_EQUAL, SP.LISTS)
+
+
+def test_split_equals_the_masked_runs_at_2048_samples(tx, monkeypatch):
+    equal_to_masked_runs(tx, monkeypatch, "float", "lamp", False, (2048,), (130,))
+
+
+# ---- 3. linearity ----------------------------------------------------------------------------------------------------------------------------------------------
+
+def test_combine_is_the_irradiance_under_the_recoloured_texture(tx):
+    from texir_code_amd import irtsplit
+    from conftest import rel_l2
+    K, lab = SP.labels("bands")
+    full, mask, hdr = world(tx, "float")
+    c = np.array([0.5, 2.0, 4.0], np.float32)
+    ids, use = ids_of(130), TC.listed(SP.SCENE, 130)
+    E = split(full, lab, K, 128, ids)[:, use]
+    mask.set_texture(np.ascontiguousarray(hdr * c[lab][..., None]))
+    want = generate(mask, 128, ids)[use]
+    err = rel_l2(irtsplit.combine(E, c), want)
+    print("irt_split linearity: combine(E, (0.5, 2, 4)) against irt_generate on the recoloured texture, relative L2 %.3e" % err)
+    assert err <= 1e-3
+
+
+# ---- 4. purity -----------------------------------------------------------------------------------------------------------------------------------------------------
+
+def test_result_is_a_pure_function_of_the_inputs(tx):
+    from texir_code_amd import _lib
+    K, lab = SP.labels("random8")
+    full, _, _ = world(tx, "float")
+    N, n = 128, 130
+    ids, use = ids_of(n), TC.listed(SP.SCENE, n)
+    base = split(full, lab, K, N, ids)
+    unlisted = np.ones(base.shape[1], bool)
+    unlisted[use] = False
+    assert (base[:, unlisted] == SENTINEL).all() and np.isfinite(base).all() and (base[:, use] != SENTINEL).all()
+    assert np.array_equal(base, split(full, lab, K, N, ids)), "second run"
+    perm = torch.from_numpy(np.random.default_rng(3).permutation(n)).cuda()
+    assert np.array_equal(base, split(full, lab, K, N, ids[perm])), "shuffled list"
+    L = _lib.lib()
+    per_texel = int(L.texir_irt_split_workspace_bytes(1, N, K))
+    assert per_texel == 12 * K * TC.n_parts(N, "group")
+    assert np.array_equal(base, split(full, lab, K, N, ids, max_workspace_bytes=64 * per_texel)), "three slices (64 + 64 + 2 texels)"
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        on_side = split(full, lab, K, N, ids)
+    torch.cuda.current_stream().wait_stream(side)
+    assert np.array_equal(base, on_side), "side stream"
+    # a captured graph replayed twice, on caller-owned buffers with guard words behind `out` and behind the workspace
+    pos, nrm, shift = texel_inputs()
+    Nt, guard = pos.shape[0], 64
+    labels = torch.from_numpy(lab).cuda()
+    out = torch.full((K * Nt * 3 + guard,), SENTINEL, device="cuda")
+    need = int(L.texir_irt_split_workspace_bytes(n, N, K))
+    ws = torch.full((need + guard,), 0xA5, dtype=torch.uint8, device="cuda")
+    g = torch.cuda.CUDAGraph()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(g, stream=side):
+            _lib.check(L.texir_irt_split(full.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(ids), n, Nt, N, 0, _lib.ptr(labels), K, 0, _lib.ptr(out),
+                                         _lib.ptr(ws), need, _lib.stream_ptr()))
+    torch.cuda.current_stream().wait_stream(side)
+    for _ in range(2):
+        out.fill_(SENTINEL)
+        ws[:need].zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(base, out[:K * Nt * 3].reshape(K, Nt, 3).cpu().numpy()), "graph replay"
+        assert (out[K * Nt * 3:] == SENTINEL).all() and (ws[need:] == 0xA5).all(), "guard words"
+
+
+# ---- 5. argument errors ----------------------------------------------------------------------------------------------------------------------------------------------
+
+def test_refused_arguments_raise(tx, monkeypatch):
+    from texir_code_amd import _lib
+    K, lab = SP.labels("bands")
+    full, _, _ = world(tx, "float")
+    pos, nrm, shift = texel_inputs()
+    ids = ids_of(65)
+    labels = torch.from_numpy(lab)
+    for bad_k in (0, 9, -1):
+        with pytest.raises(_lib.TexirError, match="K must be in 1..8"):
+            full.irt_split(pos, nrm, shift, 64, labels, bad_k, texel_ids=ids)
+    with pytest.raises(_lib.TexirError, match="labels"):
+        full.irt_split(pos, nrm, shift, 64, None, K, texel_ids=ids)
+    for bad_n in (0, -64):
+        with pytest.raises(_lib.TexirError, match="bad sizes"):
+            full.irt_split(pos, nrm, shift, bad_n, labels, K, texel_ids=ids)
+    L = _lib.lib()
+    Nt = pos.shape[0]
+    out = torch.full((K, Nt, 3), SENTINEL, device="cuda")
+    need = int(L.texir_irt_split_workspace_bytes(65, 64, K))
+    ws = torch.zeros(need, dtype=torch.uint8, device="cuda")
+    dl = labels.cuda()
+    call = lambda n_ids, w, nbytes, sc=full: L.texir_irt_split(sc.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(ids), n_ids, Nt, 64, 0, _lib.ptr(dl), K, 0,
+                                                               _lib.ptr(out), _lib.ptr(w), nbytes, _lib.stream_ptr())
+    with pytest.raises(_lib.TexirError, match="workspace"):
+        _lib.check(call(65, ws, need - 1))
+    with pytest.raises(_lib.TexirError, match="workspace"):
+        _lib.check(call(65, None, need))
+    _lib.check(call(0, None, 0))                                # an empty list is a no-op, whatever the workspace
+    torch.cuda.synchronize()
+    assert (out == SENTINEL).all()
+    monkeypatch.setenv("TEXIR_BVH_WIDTH", "2")
+    geo, _ = TC.golden_geo(SP.SCENE)
+    binary = tx.Scene(geo.verts, geo.tris, geo.tri_uvs, geo.hdr)
+    with pytest.raises(_lib.TexirError, match="4-wide tree"):
+        _lib.check(call(65, ws, need, binary))
+    torch.cuda.synchronize()
+    assert (out == SENTINEL).all()
+
+
+# ---- 6. the stage and the command ------------------------------------------------------------------------------------------------------------------------------------
+
+def test_stage_writes_the_class_files_and_relight_round_trips(tmp_path, capsys):
+    from texir_code_amd import datasets as D, io_formats as IO, irtsplit, tools
+    from texir_code_amd.trainer import exp_runner as ER
+
+    def run(tag, extra):
+        root = str(tmp_path / tag)
+        D.write_synthetic_dataset(root, T=2000, texel_res=64, tex_res=64, n_side=2)
+        conf = str(tmp_path / (tag + ".conf"))
+        D.write_conf(conf, root, cube_res=16, spp=(64, 16), model="irt")
+        if extra:
+            txt = open(conf).read()
+            assert "batch_size = 1" in txt
+            with open(conf, "w") as f:
+                f.write(txt.replace("batch_size = 1", "batch_size = 1\n    " + "\n    ".join(extra), 1))
+        d = os.path.join(root, "vrproc", "hdr_texture")
+        before = set(os.listdir(d))
+        ER.main(["--conf", conf, "--trainstage", "IrrT", "--gpu", "0"])
+        return d, {f: open(os.path.join(d, f), "rb").read() for f in sorted(set(os.listdir(d)) - before)}
+
+    d0, plain = run("plain", [])
+    d1, split = run("split", ["irt_split = lights", "irt_split_unit = true"])
+    # without the key: no new file; with it: the class files and nothing else, every other file byte for byte
+    assert "0_irr_texture.hdr" in plain and not [f for f in plain if "class" in f or "unit" in f]
+    assert sorted(set(split) - set(plain)) == sorted("0_irr_texture_%s%d.hdr" % (w, k) for w in ("class", "unit") for k in (0, 1))
+    assert all(split[f] == plain[f] for f in plain)
+    hdr = IO.read_hdr(os.path.join(d1, "hdr_texture.hdr"))
+    lab = irtsplit.labels_from_radiance(hdr, 0.0)
+    print("stage: %.2f %% of the dataset's texels are lights" % (100.0 * lab.mean()))
+    full = IO.read_hdr(os.path.join(d1, "0_irr_texture.hdr")).astype(np.float64)
+    E = np.stack([IO.read_hdr(os.path.join(d1, "0_irr_texture_class%d.hdr" % k)) for k in (0, 1)]).astype(np.float64)
+    assert E[0].max() > 0 and (lab.max() == 0 or E[1].max() > 0)
+    # an RGBE pixel keeps 8 bits below its largest channel's power of two: each file is off by at most 2^-7 of that channel
+    quant = 2.0 ** -7 * (E.max(-1).sum(0) + full.max(-1))[..., None]
+    # before the files: the class sums and the plain sum add the same non-negative terms in float32, n_acc roundings each (trace_cases.n_acc)
+    acc = 2 * TC.n_acc(64, "group", TC.n_parts(64, "group")) * 2.0 ** -24
+    assert (np.abs(E.sum(0) - full) <= quant + acc * full).all()
+    assert tools.main(["relight-irt", d1, "--class", "1", "--colour", "1,1,1"]) == 0
+    relit = IO.read_hdr(os.path.join(d1, "0_irr_texture_relit.hdr")).astype(np.float64)
+    assert (np.abs(relit - full) <= quant + 2.0 ** -7 * relit.max(-1)[..., None] + acc * full).all()
+    assert tools.main(["relight-irt", d1, "--class", "1", "--colour", "1,1,1"]) == 1            # refuses to overwrite
+    os.remove(os.path.join(d1, "0_irr_texture_relit.hdr"))
+    assert tools.main(["relight-irt", d1, "--class", "1", "--colour", "2,1,0.5", "--replace"]) == 0
+    F1 = IO.read_hdr(os.path.join(d1, "0_irr_texture_unit1.hdr")).astype(np.float64)
+    want = E[0] + F1 * np.array([2.0, 1.0, 0.5])
+    relit = IO.read_hdr(os.path.join(d1, "0_irr_texture_relit.hdr")).astype(np.float64)
+    assert (np.abs(relit - want) <= 2.0 ** -7 * relit.max(-1)[..., None] + 1e-6 * want).all()
+    assert tools.main(["relight-irt", d0, "--class", "0", "--colour", "1,1,1"]) == 1            # no class files there

@@ -59,6 +59,9 @@ def lib():
             "texir_diffuse_irradiance": [vp, vp, vp, vp, i64, i32, i32, vp, vp],
         }
         sig["texir_irt_kernel_name"] = [vp, i64, i32, C.c_char_p, i32]
+        L.texir_irt_split_workspace_bytes.argtypes = [i64, i32, i32]
+        L.texir_irt_split_workspace_bytes.restype = i64
+        sig["texir_irt_split"] = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, i32, vp, vp, i64, vp]
         sig["texir_loss_forward"] = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
         sig["texir_scene_set_corner_normals"] = [vp, vp]
         sig["texir_gbuffer_cast"] = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]

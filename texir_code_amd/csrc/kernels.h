@@ -78,4 +78,9 @@ float atlas_fill_cell(const float bounds[6], int64_t n_src, float cell);        
 hipError_t launch_atlas_fill(const float* pos, const float* nrm, int64_t Nt, const int32_t* source_ids, int64_t n_src, const int32_t* hole_ids, int64_t n_holes,
                              const float bounds[6] /*host*/, float cos_fill, float max_dist, float cell, int32_t* src, float* dist2 /*nullable*/,
                              unsigned long long* stats /*nullable*/, void* workspace, hipStream_t st);
+// irtsplit.hip: per-class IrT in one traced pass (the 64-texel plan of irt_group_kernel; needs the 4-wide tree)
+size_t irt_split_workspace_bytes(int64_t n_ids, int N, int K);       // 0 for arguments the launch would refuse
+hipError_t launch_irt_split(const SceneDev& sc, const float* tex_row_major, const uint8_t* labels, const float* pos, const float* nrm, const float* shift,
+                            const int32_t* ids /*nullable: all Nt*/, int64_t n_ids, int64_t Nt, int N, int mode, int K, int unit, float* out /*[K][Nt][3]*/,
+                            float* partial /*>= irt_split_workspace_bytes()*/, hipStream_t st);
 }  // namespace texir

@@ -137,6 +137,11 @@ class TracerO3d(nn.Module):
         self.index_texture = None if idx is None else np.ascontiguousarray(idx)
         if idx is not None:
             self.atlas_hw = tuple(int(v) for v in idx.shape[:2])
+        # train.irt_split (optional key): none (default) | lights | seg | <8-bit png of the radiance texture's size>: forward() also splits the irradiance by
+        # the class of the texels it comes from (irt_split_labels below; Scene.irt_split); train.irt_split_unit adds the unit-radiance split
+        self.irt_split = str(conf.get("train.irt_split", "none"))
+        self.irt_split_unit = conf.get_bool("train.irt_split_unit", False)
+        self.ir_split = self.ir_split_unit = None
         # optional exact texel G-buffer written by the synthetic generator (bypasses the panorama gather)
         self.texel_gbuffer_path = _sibling(self.path_traced_mesh, "texel_gbuffer.npz")
 
@@ -176,6 +181,32 @@ class TracerO3d(nn.Module):
         z = np.load(self.texel_gbuffer_path)
         self.position_texture = torch.from_numpy(z["position"]).to(self.device)
         self.normal_texture = torch.from_numpy(z["normal"]).to(self.device)
+
+    def irt_split_labels(self):
+        """(labels uint8 [Ht,Wt] in the orientation of the scene's texture, K) of train.irt_split:
+          lights  the reference's lamp rule (models/test_nvdiffrast.py:109-110): intensity of the un-exposed radiance above 0.5 -> class 1, else 0;
+          seg     0_seg_gray.png beside the mesh: wall (45) -> 1, floor (46) -> 2, everything else 0 -- the classes MatEditingRunner edits;
+          <png>   an 8-bit single-channel image of the texture's size in FILE orientation (as hdr_texture.hdr), values 0..7 = the class."""
+        from . import irtsplit
+        tex = self.texture.numpy()
+        how = self.irt_split
+        if how.lower() == "lights":
+            return irtsplit.labels_from_radiance(tex, self.conf.get_float("train.hdr_exposure")), 2
+        if how.lower() == "seg":
+            img = IO.read_png(_sibling(self.path_traced_mesh, "0_seg_gray.png"))
+            img = img[..., 0] if img.ndim == 3 else img
+            lab, K = irtsplit.labels_from_seg(img, {45: 1, 46: 2}), 3
+        else:
+            img = IO.read_png(how)
+            img = img[..., 0] if img.ndim == 3 else img
+            if img.dtype != np.uint8:
+                raise ValueError("train.irt_split = %s: the label image must be an 8-bit png, got %s" % (how, img.dtype))
+            lab, K = img, int(img.max()) + 1
+            if K > 8:
+                raise ValueError("train.irt_split = %s: classes 0..%d, at most 8 per split (regroup the classes)" % (how, K - 1))
+        if lab.shape != tex.shape[:2]:
+            raise ValueError("train.irt_split = %s: the label image is %r, the radiance texture %r" % (how, lab.shape, tex.shape[:2]))
+        return np.ascontiguousarray(lab[::-1]), K                    # (the scene holds the texture flipped: cv2.flip(texture, 0))
 
     # -- tracer_o3d_irt.py:145-180 ----------------------------------------------------------------------------------
     def forward(self):
@@ -224,6 +255,15 @@ class TracerO3d(nn.Module):
             self.scene.irt_generate(pos, nrm, shift, int(self.sample_l[0]), self.sample_type[0], texel_ids=ids, out=irr)
         with phases.phase("assemble_shards"):
             dist_util.assemble_shards(irr, ids_all)             # (one all_gather of the ranks' own texel values; no-op for one rank)
+        if self.irt_split.lower() != "none":
+            if world > 1:
+                raise NotImplementedError("train.irt_split runs on one GPU (the split is not sharded)")
+            with phases.phase("irt_split"):
+                labels, K = self.irt_split_labels()
+                args = (pos, nrm, shift, int(self.sample_l[0]), torch.from_numpy(labels), K)
+                self.ir_split = self.scene.irt_split(*args, mode=self.sample_type[0], texel_ids=ids).reshape(K, H, W, 3)
+                if self.irt_split_unit:
+                    self.ir_split_unit = self.scene.irt_split(*args, mode=self.sample_type[0], texel_ids=ids, unit=True).reshape(K, H, W, 3)
         self.ir_texture = irr.reshape(H, W, 3)
         return self.ir_texture
 

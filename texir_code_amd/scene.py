@@ -153,6 +153,50 @@ class Scene:
                                                  int(n_samples), MODES[mode], _lib.ptr(out), _lib.ptr(st), _lib.stream_ptr()))
         return (out, st) if stats else out
 
+    # -- irradiance split by source label (include/texir_hip.h texir_irt_split) ---------------------------
+    def irt_split(self, pos, nrm, shift, n_samples, labels, n_classes, mode="uniform", texel_ids=None, unit=False, out=None, max_workspace_bytes=4 << 30):
+        """per-class irradiance in one traced pass: labels [Ht,Wt] uint8 in the orientation of the scene's texture, n_classes in 1..8 -> out
+        [n_classes, Nt, 3]; out[k] is bit for bit what irt_generate in its 64-texel form gives for the texture tex * [label == k] (unit=True: for the
+        indicator texture of class k).  The id list is walked in slices that are multiples of 64 texels so that the partial-sum workspace stays
+        under max_workspace_bytes; the cuts do not change a bit.  Only listed texels are written."""
+        pos = _dev_f32(pos, self.device).reshape(-1, 3)
+        nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
+        Nt = pos.shape[0]
+        shift = _dev_f32(shift, self.device).reshape(Nt, 2)
+        K, N = int(n_classes), int(n_samples)
+        if labels is not None:
+            if not torch.is_tensor(labels):
+                labels = torch.from_numpy(np.ascontiguousarray(labels))
+            if labels.dtype != torch.uint8 or tuple(labels.shape) != tuple(self.tex_shape[:2]):
+                raise ValueError("labels must be uint8 [%d,%d]" % tuple(self.tex_shape[:2]))
+            labels = labels.to(device=self.device).contiguous()
+        if out is None:
+            out = torch.zeros((max(K, 0), Nt, 3), device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (K, Nt, 3) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 [%d,%d,3]" % (K, Nt))
+        ids = None
+        n = Nt
+        if texel_ids is not None:
+            ids = texel_ids.to(device=self.device, dtype=torch.int32).contiguous()
+            n = ids.numel()
+        if n == 0:
+            return out
+        L = _lib.lib()
+        per_texel = int(L.texir_irt_split_workspace_bytes(1, N, K))       # (0 for arguments the library refuses: the call below then reports them)
+        step = n
+        if per_texel > 0 and per_texel * n > int(max_workspace_bytes):
+            step = max(64, int(max_workspace_bytes) // per_texel // 64 * 64)
+            if ids is None:
+                ids = torch.arange(Nt, device=self.device, dtype=torch.int32)
+        ws_bytes = max(per_texel * step, 16)
+        ws = torch.empty(ws_bytes, device=self.device, dtype=torch.uint8)
+        for first in range(0, n, step):
+            cnt = min(step, n - first)
+            part = None if ids is None else ids[first:first + cnt]
+            _lib.check(L.texir_irt_split(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(part), cnt, Nt, N, MODES[mode], _lib.ptr(labels),
+                                         K, int(bool(unit)), _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()))
+        return out
+
 
 def generate_dir(normals, num_sample_dir, shift, mode="uniform", roughness=None):
     """utils/sample_util.py:63-146 on the GPU; `shift` [b,2] is the torch.rand(b,1,2) of :102 made explicit."""

@@ -38,6 +38,13 @@ a filled texel is not seen by the view it borrows from, and under the `pano` G-b
 train.texel_gbuffer = raster the IrT stage computes irradiance at filled texels too.  atlas_fill.npz (src int32 [H,W], -1 elsewhere, file orientation) is
 written beside the atlas so that later gathers can be completed the same way; with --seg a filled texel takes its source's class and gutters stay 0.
 Without --fill every file is what the command wrote before the option existed, bit for bit.
+
+    python -m texir_code_amd.tools relight-irt <dir> --class k --colour r,g,b [--replace]
+
+From the files an IrT stage with train.irt_split wrote into <dir> (0_irr_texture_class<j>.hdr, the irradiance that comes from the texels of class j):
+0_irr_texture_relit.hdr = sum_{j != k} E_j + colour * E_k -- class k's radiance scaled per channel (1,1,1 gives the plain texture back, 0,0,0 switches the
+class off).  --replace: class k's texels become ONE colour instead, colour * 0_irr_texture_unit<k>.hdr (train.irt_split_unit; the reference's "lamp texels
+become one colour", models/test_nvdiffrast.py:109-110).  Irradiance is linear in the radiance texture: nothing is traced.  Existing files are not overwritten.
 """
 import sys
 
@@ -154,7 +161,64 @@ def parse_bake_atlas(argv):
             "fill_dist": fd, "fill_cos": fc}
 
 
+def relight_irt(directory, k, colour, replace=False):
+    """-> the path written.  FileExistsError / FileNotFoundError / ValueError name what is wrong"""
+    import os
+    from . import irtsplit
+    dst = os.path.join(directory, "0_irr_texture_relit.hdr")
+    if os.path.exists(dst):
+        raise FileExistsError("%s exists: not overwritten" % dst)
+    E = []
+    while os.path.exists(os.path.join(directory, "0_irr_texture_class%d.hdr" % len(E))):
+        E.append(np.asarray(IO.read_hdr(os.path.join(directory, "0_irr_texture_class%d.hdr" % len(E))), np.float32))
+    if not E:
+        raise FileNotFoundError("no 0_irr_texture_class0.hdr in %s: run the IrT stage with train.irt_split" % directory)
+    if not 0 <= k < len(E):
+        raise ValueError("--class %d: %s holds classes 0..%d" % (k, directory, len(E) - 1))
+    E = np.stack(E)
+    if replace:
+        unit = os.path.join(directory, "0_irr_texture_unit%d.hdr" % k)
+        if not os.path.exists(unit):
+            raise FileNotFoundError("--replace needs %s: run the IrT stage with train.irt_split_unit = true" % unit)
+        F = np.zeros_like(E)
+        F[k] = IO.read_hdr(unit)
+        out = irtsplit.replace_constant(E, F, k, colour)
+    else:
+        out = irtsplit.combine(E, [colour if j == k else 1.0 for j in range(len(E))])
+    IO.write_hdr(dst, np.ascontiguousarray(out, np.float32))
+    return dst
+
+
 def main(argv):
+    if len(argv) >= 2 and argv[0] == "relight-irt":
+        opt, rest, flags = {"--class": None, "--colour": None}, [], []
+        it = iter(argv[1:])
+        for a in it:
+            key = a.split("=", 1)[0]
+            if key in opt:
+                opt[key] = a.split("=", 1)[1] if "=" in a else next(it, None)
+            elif a.startswith("--"):
+                flags.append(a)
+            else:
+                rest.append(a)
+        try:
+            k = int(opt["--class"])
+            colour = tuple(float(v) for v in opt["--colour"].split(","))
+            if len(rest) != 1 or len(colour) != 3 or any(f != "--replace" for f in flags):
+                raise ValueError
+        except (TypeError, ValueError, AttributeError):
+            print("relight-irt needs <dir> --class k --colour r,g,b [--replace]")
+            return 2
+        try:
+            dst = relight_irt(rest[0], k, colour, "--replace" in flags)
+        except (FileExistsError, FileNotFoundError) as e:
+            print(e)
+            return 1
+        except ValueError as e:
+            print(e)
+            return 2
+        print("wrote", dst)
+        return 0
     if len(argv) >= 3 and argv[0] == "bake-atlas":
         from . import atlas
         try:

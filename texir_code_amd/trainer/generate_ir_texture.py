@@ -83,6 +83,12 @@ class IrrTextureRunner:
                 IO.write_hdr(target, arr)          # Radiance RGBE (RLE scanlines) like cv2.imwrite('.hdr') (generate_ir_texture.py:82)
             if self.irt_pad != "none":
                 self._write_irt(irr_texture, target.replace("0_irr_texture.hdr", "irt.hdr"))
+            # train.irt_split (models.TracerO3d): the irradiance per class of the texels it comes from, beside the plain file
+            for what, split in (("class", getattr(self.model, "ir_split", None)), ("unit", getattr(self.model, "ir_split_unit", None))):
+                if split is not None:
+                    with phases.phase("write_hdr", sync=False):
+                        for k in range(split.shape[0]):
+                            IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_%s%d.hdr" % (what, k)), split[k].cpu().numpy())
         return irr_texture
 
     def _write_irt(self, irr_texture, path):
