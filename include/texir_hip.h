@@ -566,6 +566,68 @@ TEXIR_API int texir_atlas_fill(const float* pos /*dev*/, const float* nrm /*dev*
                        int32_t* src /*dev [Nt]*/, float* dist2 /*dev [Nt], nullable*/, uint64_t* stats /*dev [2], nullable*/, void* workspace /*dev*/,
                        void* stream);
 
+/* ---- inserted emitters: the direct irradiance of NEW area lights per texel (csrc/irtlight.hip).  The irradiance split recolours light that is in the
+ * capture; this adds light that is not.  The reference's relighting demo leaves its "moving" half -- an emitter at a new position per frame -- to an
+ * external renderer (tools/relighting_varying.py).  Irradiance is linear in emitted radiance: an emitter of radiance c adds c * F to 0_irr_texture.hdr,
+ * with F the per-texel geometry-and-visibility factor below, traced once.  Direct light only: no bounce of the new light is computed.
+ *
+ * THE RULE.  Per texel: x = pos (already offset), n = nrm (RAW, as the IrT estimator uses it), the texel's Cranley-Patterson shift (the one
+ * texir_irt_generate takes).  Per light k: a record of 16 float32 in DEVICE memory (a recorded graph is replayed with moved lights, so the host never
+ * validates a record):
+ *     [0] kind: 0.0f = parallelogram ("quad"), 1.0f = sphere      [1..3] p: the quad's corner o, or the sphere's centre c
+ *     [4..6] a: a quad edge; sphere: a.x = radius r, a.y and a.z ignored      [7..9] b: the other quad edge (sphere: ignored)      [10..15] reserved, ignored
+ *   A record with another kind, a non-finite word among those its kind uses, a quad with a x b = 0 (or not finite) or a sphere with r <= 0 (or 4 pi r^2 not
+ *   finite) yields F = 0 for that light, and no ray is traced for it.
+ *   For sample i = 0 .. S-1:
+ *   SAMPLE      s0 = shift_wrap_clamp(ham0(i, S), shift.x), s1 = shift_wrap_clamp(ham1(i), shift.y): the Hammersley point and the wrap of
+ *               texir_irt_generate (csrc/device_common.h), in (0, 1).
+ *   QUAD        y = (o + s0 a) + s1 b;  m = a x b, RAW: its length is the area, its direction the emitting side (one-sided: a two-sided panel is two
+ *               records);  w = 1.
+ *   SPHERE      z = 1 - 2 s0;  q = sqrt(max(0, 1 - z z));  phi = 2 pi s1;  u = (q cos phi, q sin phi, z);  y = c + r u;  m = u;  w = 4 pi r^2.
+ *   GEOMETRY    d = y - x;  dd = d.d;  nd = n.d;  md = -(m.d);  g = (nd md) / (dd dd) when nd > 0, md > 0, dd > 0 and the quotient is finite, else g = 0.
+ *               A ray is traced iff g > 0.  (Two cosines over the squared distance, times the area element: there is no square root in the quad path.)
+ *   VISIBILITY  the ray (org = x, dir = d): V = 0 iff its closest hit has t < t_max, else V = 1.  Closest hit is what texir_trace_shade reports (Embree
+ *               semantics: t > 0, t in units of |dir|); no t_min, because pos is already offset.  t_max = 1 is the bake's rule; scene.Scene.irt_lights
+ *               defaults to 0.999 so that a light laid onto a surface is not shadowed by that surface.
+ *   RESULT      acc = sum_i V_i g_i in ascending i in ONE float32 accumulator;  F[k][texel] = (acc * w) / float(S).  The irradiance under an emitted
+ *               radiance c_k is c_k F[k].
+ *   WRITES      every LISTED texel is written for every k, zeros included.  Unlisted texels are untouched.  An id outside [0, Nt) is not a texel.
+ * F is a pure function of the inputs: no atomics on results, no workspace; list order, duplicates, launch shape and stream do not change a bit.
+ *
+ * FLOAT32 OPERATION SEQUENCE (each operation separately rounded, no contraction; sqrt and / correctly rounded; tau32 = 6.28318548 and fourpi32 = 12.5663710,
+ * the float32 neighbours of 2 pi and 4 pi, off by less than 0.5 u relative).  s0 and s1 use IEEE additions, comparisons and one exact scaling only (ham0
+ * of an S that is no power of two: one float64 quotient rounded to float32), so a restatement on any IEEE machine gives the same bits; the bounds below start
+ * from them as exact float32 values.
+ *     quad:    y_i = (o_i + s0 * a_i) + s1 * b_i;   m_x = a_y * b_z - a_z * b_y,  m_y = a_z * b_x - a_x * b_z,  m_z = a_x * b_y - a_y * b_x
+ *     sphere:  z = 1 - 2 * s0;   q = sqrt(max(0, 1 - z * z));   phi = tau32 * s1;   u = (q * cosf(phi), q * sinf(phi), z);   y_i = c_i + r * u_i;   m = u;
+ *              w = (fourpi32 * r) * r
+ *     d_i = y_i - x_i;   dd = (d_x d_x + d_y d_y) + d_z d_z;   nd = (n_x d_x + n_y d_y) + n_z d_z;   md = -((m_x d_x + m_y d_y) + m_z d_z)
+ *     g = (nd * md) / (dd * dd);   acc = acc + g  (visible samples, ascending i);   F = (acc * w) / float(S)
+ * ROUNDING BOUND (first order, u = 2^-24; the inputs x, n, the record, s0, s1 are exact float32 values; the tests multiply every bound by their factor K).
+ * With e_i the bound of d_i and f_i the bound of m_i:
+ *     quad:    e_i = u (3 Y_i + |d_i|),  Y_i = |o_i| + |s0 a_i| + |s1 b_i|      (two products, two sums, the difference)
+ *              f_x = 2 u (|a_y b_z| + |a_z b_y|), f_y and f_z alike              (two products, the difference)
+ *     sphere:  |dz| <= u |z|;   A = 1 - z z:  |dA| <= 2 |z| |dz| + u z z + u |A|;   |dq| <= min(|dA| / (2 sqrt(max(A - |dA|, 0))), sqrt(|dA|)) + u q
+ *              |dphi| <= 1.5 u phi;   cosf, sinf taken as accurate to 4 ulp (OpenCL's limit):  |dcos| <= |dphi| + 8 u |cos phi|,  |dsin| alike
+ *              f_x = |cos phi| |dq| + q |dcos| + u |u_x|,  f_y alike with sin,  f_z = |dz|
+ *              e_i = r f_i + u (|r u_i| + |y_i| + |d_i|)                          (the product, the sum, the difference)
+ *     |ddd| <= 3 u dd + 2 sum_i |d_i| e_i
+ *     |dnd| <= 3 u N1 + sum_i |n_i| e_i,  N1 = sum_i |n_i d_i|;   the test nd > 0 is decided unless |nd| <= |dnd|
+ *     |dmd| <= 3 u M1 + sum_i |m_i| e_i + sum_i |d_i| f_i,  M1 = sum_i |m_i d_i|;   the test md > 0 is decided unless |md| <= |dmd|
+ *     |dg|  <= |g| (3 u + 2 |ddd| / dd) + (|dnd| |md| + |nd| |dmd|) / dd^2       (the two products and the quotient)
+ *     the direction of the ray carries e_i per component
+ *     |dF|  <= (w / S) ((S + 4) u sum_i |g_i| + sum_i |dg_i|)                     (S - 1 additions; w: 2.5 u; the product and the quotient by S)
+ *
+ *   pos, nrm [Nt,3], shift [Nt,2] dev;  texel_ids [n_ids] i32 dev, nullable = all Nt texels (n_ids ignored; pass them in Morton order: a wave is 64
+ *   consecutive ids);  lights dev [K][16], K in 0..8;  S in 1..65536;  t_max finite;  F dev [K][Nt].
+ *   stats dev u64[2], nullable: += samples with g > 0 (the rays traced), and the visible ones; one atomic add per wave and counter.
+ * K outside 0..8 (reported before any null buffer), S outside 1..65536, a t_max that is not finite, negative counts and a null buffer are errors with a
+ * texir_last_error() text.  K = 0 and an empty list return 0 and write nothing.
+ * Caller-owned buffers, the caller's stream, no allocation and no synchronisation: the call records into a hipGraph. */
+TEXIR_API int texir_irt_lights(const texir_scene* scene, const float* pos /*dev [Nt,3]*/, const float* nrm /*dev [Nt,3], raw*/, const float* shift /*dev [Nt,2]*/,
+                       const int32_t* texel_ids /*dev, nullable = all Nt*/, int64_t n_ids, int64_t Nt, const float* lights /*dev [K][16]*/, int32_t K /*0..8*/,
+                       int32_t S /*1..65536*/, float t_max, float* F /*dev [K][Nt]*/, uint64_t* stats /*dev [2], nullable*/, void* stream);
+
 /* ---- host-side codec loops of the file formats around the path (both take HOST pointers) ----------------------------
  * PNG scanline un-filtering (filters 0-4, PNG spec 9.2) of zlib-inflated IDAT data: raw [H][stride+1] -> out [H][stride]; replaces the
  * decode half of cv2.imread("0.png", -1) (models/tracer_o3d_irt.py:91, datasets/dataset.py:489-492). */

@@ -102,6 +102,7 @@ def lib():
         L.texir_atlas_fill_cell.argtypes = [vp, i64, f32]
         L.texir_atlas_fill_cell.restype = f32
         sig["texir_atlas_fill"] = [vp, vp, i64, vp, i64, vp, i64, vp, f32, f32, f32, vp, vp, vp, vp, vp]
+        sig["texir_irt_lights"] = [vp, vp, vp, vp, vp, i64, i64, vp, i32, i32, f32, vp, vp, vp]
         sig["texir_png_unfilter"] = [vp, i32, i32, i32, vp]
         L.texir_hdr_decode_scanlines.argtypes = [vp, i64, i32, i32, vp]
         L.texir_hdr_decode_scanlines.restype = i64

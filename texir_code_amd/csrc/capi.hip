@@ -765,4 +765,22 @@ int texir_atlas_fill(const float* pos, const float* nrm, int64_t Nt, const int32
     return TEXIR_OK;
 }
 
+/* ---- inserted emitters, csrc/irtlight.hip: the direct irradiance factor F of K new area lights per listed texel (the "moving" half of
+ * tools/relighting_varying.py leaves the reference for an external renderer; include/texir_hip.h states the rule) ---- */
+int texir_irt_lights(const texir_scene* s, const float* pos, const float* nrm, const float* shift, const int32_t* texel_ids, int64_t n_ids, int64_t Nt,
+                     const float* lights, int32_t K, int32_t S, float t_max, float* F, uint64_t* stats, void* stream)
+{
+    // (K first: a caller that sized `lights` and `F` by a bad K may hold no buffer at all)
+    if (K < 0 || K > 8) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: K must be in 0..8, got %d (call again for further lights: the factors add)", K);
+    if (S < 1 || S > 65536) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: S must be in 1..65536, got %d", S);
+    if (!(t_max - t_max == 0.0f)) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: t_max must be finite");
+    if (Nt < 0 || (texel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: negative texel count");
+    if (Nt >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: Nt too large");
+    const int64_t n = texel_ids ? n_ids : Nt;
+    if (K == 0 || n == 0) return TEXIR_OK;
+    if (!s || !pos || !nrm || !shift || !lights || !F) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: null argument (scene, pos, nrm, shift, lights and F are required)");
+    HIP_TRY(launch_irt_lights(dev_of(s), pos, nrm, shift, texel_ids, n, Nt, lights, K, S, t_max, F, (unsigned long long*)stats, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 }  // extern "C"

@@ -1,0 +1,142 @@
+// Inserted emitters: the direct irradiance of new area lights per texel (include/texir_hip.h texir_irt_lights states the rule, the float32 operation
+// sequence and its rounding bound; this file follows that text operation by operation, contraction off).  The reference cannot do this: the "moving" half of
+// tools/relighting_varying.py hands the scene to an external renderer.  Irradiance is linear in emitted radiance, so an emitter of radiance c adds c * F to
+// 0_irr_texture.hdr, with F the per-texel geometry-and-visibility factor this kernel integrates over the emitter's surface.
+//
+// One lane is one listed texel, 64 per wave over the caller's (Morton-ordered) id list: 64 neighbouring texels shooting at ONE small emitter are about as
+// coherent a ray bundle as the traversal gets.  A work item is (64-texel group, light); items are dealt statically: wave w of the grid takes items w,
+// w + waves, ... -- no work counter, no wave waits on another, every loop is bounded by K, S, the item count or the traversal's own bounds.  The light record
+// is a wave-uniform (scalar) load; the sample loop runs over i for the whole wave; a sample no lane of the wave needs is skipped by ballot.  Visibility is ONE
+// closest-hit query (device_common.h trace_closest, used as it is, as texbake.hip calls it): occluded iff the closest hit has t < t_max.
+// F is a pure function of the inputs: one float32 accumulator per (texel, light) in ascending i, no atomics on results, no workspace.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernels.h"
+
+namespace texir {
+
+// every product, sum and quotient below is its own rounded float32 operation: the header states the arithmetic and the tests restate it
+#pragma clang fp contract(off)
+
+constexpr bool kLightCull = true;
+constexpr int kLightLstk = kLdsStack / 2;          // 8-byte entries: 24 KiB of traversal stack per block, as the bake keeps
+constexpr float kTwoPi32 = 6.28318548202514648f, kFourPi32 = 12.5663709640502930f;      // the float32 neighbours of 2 pi and 4 pi
+
+__device__ __forceinline__ bool light_finite(float x) { return x - x == 0.f; }
+
+__device__ __forceinline__ unsigned long long light_wave_sum(unsigned long long x)
+{
+    for (int o = 32; o > 0; o >>= 1) x += (unsigned long long)__shfl_xor((long long)x, o, 64);
+    return x;
+}
+
+template <int WIDTH>
+__global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm, const float* __restrict__ shift,
+                                                            const int32_t* __restrict__ ids, int64_t n, int64_t Nt, const float* __restrict__ lights, int K, int S,
+                                                            float t_max, float* __restrict__ F, unsigned long long* __restrict__ stats)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (wave-uniform: the item loop and the sample loop stay scalar)
+    const int64_t gw = (int64_t)blockIdx.x * (kBlock / 64) + wave, nw = (int64_t)gridDim.x * (kBlock / 64);
+    const int64_t n_items = ((n + 63) / 64) * K;
+    uint32_t cn = 0, ct = 0;
+    unsigned long long n_traced = 0, n_visible = 0;
+    for (int64_t item = gw; item < n_items; item += nw) {
+        const int64_t group = item / K;
+        const int k = (int)(item - group * K);
+        const int64_t i = group * 64 + lane;
+        int64_t tex = i < n ? (ids ? (int64_t)ids[i] : i) : -1;
+        if (tex >= Nt) tex = -1;                                           // an id outside [0, Nt) is not a texel: nothing is read or written for it
+        const bool live = tex >= 0;
+        float px = 0.f, py = 0.f, pz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f, sh0 = 0.f, sh1 = 0.f;
+        if (live) {
+            px = pos[3 * tex]; py = pos[3 * tex + 1]; pz = pos[3 * tex + 2];
+            nx = nrm[3 * tex]; ny = nrm[3 * tex + 1]; nz = nrm[3 * tex + 2];
+            sh0 = shift[2 * tex]; sh1 = shift[2 * tex + 1];
+        }
+        // the record: wave-uniform, scalar loads.  Device data the host never saw: everything is decided here.
+        const float* L = lights + 16 * (size_t)k;
+        const float kind = L[0];
+        const float cx = L[1], cy = L[2], cz = L[3], ax = L[4], ay = L[5], az = L[6], bx = L[7], by = L[8], bz = L[9];
+        const bool quad = kind == 0.f, sphere = kind == 1.f;
+        float mx = 0.f, my = 0.f, mz = 0.f, w = 1.f;
+        bool valid = light_finite(cx) && light_finite(cy) && light_finite(cz) && light_finite(ax);
+        if (quad) {
+            mx = ay * bz - az * by;
+            my = az * bx - ax * bz;
+            mz = ax * by - ay * bx;
+            // (finite m: every word of a and b is finite)
+            valid = valid && light_finite(mx) && light_finite(my) && light_finite(mz) && light_finite(ay) && light_finite(az) && light_finite(bx) && light_finite(by) &&
+                    light_finite(bz) && (mx != 0.f || my != 0.f || mz != 0.f);
+        } else if (sphere) {
+            w = (kFourPi32 * ax) * ax;
+            valid = valid && ax > 0.f && light_finite(w);
+        } else valid = false;
+
+        float acc = 0.f;
+        uint32_t it_traced = 0, it_visible = 0;
+        if (valid) {                                                        // (wave-uniform)
+            for (int s = 0; s < S; s++) {
+                const float s0 = shift_wrap_clamp(ham0((uint32_t)s, (uint32_t)S), sh0);
+                const float s1 = shift_wrap_clamp(ham1((uint32_t)s), sh1);
+                float yx, yy, yz;
+                if (quad) {
+                    yx = (cx + s0 * ax) + s1 * bx;
+                    yy = (cy + s0 * ay) + s1 * by;
+                    yz = (cz + s0 * az) + s1 * bz;
+                } else {
+                    const float z = 1.f - 2.f * s0;
+                    const float q = sqrtf(fmaxf(0.f, 1.f - z * z));
+                    const float phi = kTwoPi32 * s1;
+                    mx = q * cosf(phi); my = q * sinf(phi); mz = z;
+                    yx = cx + ax * mx; yy = cy + ax * my; yz = cz + ax * mz;
+                }
+                const float dx = yx - px, dy = yy - py, dz = yz - pz;
+                const float dd = (dx * dx + dy * dy) + dz * dz;
+                const float nd = (nx * dx + ny * dy) + nz * dz;
+                const float md = -((mx * dx + my * dy) + mz * dz);
+                float g = 0.f;
+                if (live && nd > 0.f && md > 0.f && dd > 0.f) {
+                    g = (nd * md) / (dd * dd);
+                    if (!light_finite(g)) g = 0.f;
+                }
+                const bool need = g > 0.f;
+                if (!__any(need)) continue;                                 // no lane of the wave needs this sample
+                if (need) {
+                    it_traced++;
+                    const Hit hit = trace_closest<false, kLightLstk, WIDTH, kLightCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
+                    if (!(hit.slot >= 0 && hit.t < t_max)) {
+                        it_visible++;
+                        acc += g;
+                    }
+                }
+            }
+        }
+        if (live) F[(int64_t)k * Nt + tex] = (acc * w) / (float)S;          // every listed texel, zeros included
+        n_traced += it_traced; n_visible += it_visible;
+    }
+    if (stats) {
+        const unsigned long long a = light_wave_sum(n_traced), b = light_wave_sum(n_visible);
+        if (lane == 0) { atomicAdd(stats, a); atomicAdd(stats + 1, b); }
+    }
+}
+
+#pragma clang fp contract(fast)
+
+constexpr int kLightMaxBlocks = 2048;     // a fixed cap, as launch_atlas_bake's: nothing is queried per launch (the result does not depend on the grid)
+
+hipError_t launch_irt_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids, int64_t n, int64_t Nt,
+                             const float* lights, int K, int S, float t_max, float* F, unsigned long long* stats, hipStream_t st)
+{
+    if (n <= 0 || K <= 0) return hipSuccess;
+    const int64_t items = ((n + 63) / 64) * K;
+    const int64_t want = (items + (kBlock / 64) - 1) / (kBlock / 64);
+    const int grid = (int)(want < kLightMaxBlocks ? want : kLightMaxBlocks);
+    if (sc.nodes4)
+        hipLaunchKernelGGL(irt_lights_kernel<4>, dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n, Nt, lights, K, S, t_max, F, stats);
+    else
+        hipLaunchKernelGGL(irt_lights_kernel<2>, dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n, Nt, lights, K, S, t_max, F, stats);
+    return hipGetLastError();
+}
+
+}  // namespace texir

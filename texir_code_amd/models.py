@@ -142,6 +142,11 @@ class TracerO3d(nn.Module):
         self.irt_split = str(conf.get("train.irt_split", "none"))
         self.irt_split_unit = conf.get_bool("train.irt_split_unit", False)
         self.ir_split = self.ir_split_unit = None
+        # train.irt_lights (optional key): none (default) | <json of inserted emitters, irtlight.load>: forward() also traces the direct irradiance factor of
+        # every listed light at train.irt_light_samples (64) samples per texel (Scene.irt_lights)
+        self.irt_lights = str(conf.get("train.irt_lights", "none"))
+        self.irt_light_samples = conf.get_int("train.irt_light_samples", 64)
+        self.ir_lights = None
         # optional exact texel G-buffer written by the synthetic generator (bypasses the panorama gather)
         self.texel_gbuffer_path = _sibling(self.path_traced_mesh, "texel_gbuffer.npz")
 
@@ -264,6 +269,13 @@ class TracerO3d(nn.Module):
                 self.ir_split = self.scene.irt_split(*args, mode=self.sample_type[0], texel_ids=ids).reshape(K, H, W, 3)
                 if self.irt_split_unit:
                     self.ir_split_unit = self.scene.irt_split(*args, mode=self.sample_type[0], texel_ids=ids, unit=True).reshape(K, H, W, 3)
+        if self.irt_lights.lower() != "none":
+            if world > 1:
+                raise NotImplementedError("train.irt_lights runs on one GPU (the light pass is not sharded)")
+            with phases.phase("irt_lights"):
+                from . import irtlight
+                records, _ = irtlight.load(self.irt_lights)
+                self.ir_lights = self.scene.irt_lights(pos, nrm, shift, torch.from_numpy(records), self.irt_light_samples, texel_ids=ids).reshape(-1, H, W)
         self.ir_texture = irr.reshape(H, W, 3)
         return self.ir_texture
 

@@ -197,6 +197,38 @@ class Scene:
                                          K, int(bool(unit)), _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()))
         return out
 
+    # -- inserted emitters (include/texir_hip.h texir_irt_lights) ------------------------------------------
+    def irt_lights(self, pos, nrm, shift, lights, n_samples, texel_ids=None, t_max=0.999, out=None, stats=False):
+        """direct irradiance factors of inserted area lights: lights [K,16] float32 records (irtlight.pack; a device tensor is used in place, so a
+        recorded graph replays with whatever the records hold then), K <= 8 -> F [K, Nt]; the irradiance under emitted radiance c_k is c_k * F[k]
+        (irtlight.add).  Any point list: texels or a view's pixels.  t_max: the ray is occluded iff its closest hit has t < t_max in units of the
+        segment to the sample point (0.999: a light laid onto a surface is not shadowed by it).  Only listed texels are written.
+        stats=True: also int64 [2] = (rays traced, visible ones)"""
+        pos = _dev_f32(pos, self.device).reshape(-1, 3)
+        nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
+        Nt = pos.shape[0]
+        shift = _dev_f32(shift, self.device).reshape(Nt, 2)
+        lights = _dev_f32(lights, self.device)
+        if lights.ndim != 2 or lights.shape[1] != 16:
+            raise ValueError("lights must be [K,16], got %r" % (tuple(lights.shape),))
+        K = lights.shape[0]
+        if out is None:
+            out = torch.zeros((K, Nt), device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (K, Nt) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float32 [%d,%d] on %s" % (K, Nt, self.device))
+        ids = None
+        n_ids = 0
+        if texel_ids is not None:
+            ids = texel_ids.to(device=self.device, dtype=torch.int32).contiguous()
+            n_ids = ids.numel()
+        st = torch.zeros(2, device=self.device, dtype=torch.int64) if stats else None
+        empty = Nt == 0 or (texel_ids is not None and n_ids == 0)          # (an EMPTY id list must not reach the library as "no list = all texels")
+        if not empty:
+            _lib.check(_lib.lib().texir_irt_lights(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(ids), n_ids, Nt,
+                                                   _lib.ptr(lights) if K else None, K, int(n_samples), float(t_max), _lib.ptr(out) if K else None, _lib.ptr(st),
+                                                   _lib.stream_ptr()))
+        return (out, st) if stats else out
+
 
 def generate_dir(normals, num_sample_dir, shift, mode="uniform", roughness=None):
     """utils/sample_util.py:63-146 on the GPU; `shift` [b,2] is the torch.rand(b,1,2) of :102 made explicit."""

@@ -45,6 +45,13 @@ From the files an IrT stage with train.irt_split wrote into <dir> (0_irr_texture
 0_irr_texture_relit.hdr = sum_{j != k} E_j + colour * E_k -- class k's radiance scaled per channel (1,1,1 gives the plain texture back, 0,0,0 switches the
 class off).  --replace: class k's texels become ONE colour instead, colour * 0_irr_texture_unit<k>.hdr (train.irt_split_unit; the reference's "lamp texels
 become one colour", models/test_nvdiffrast.py:109-110).  Irradiance is linear in the radiance texture: nothing is traced.  Existing files are not overwritten.
+
+    python -m texir_code_amd.tools light-irt <dir> --light k --colour r,g,b [--light j --colour r,g,b ...] [--base <file>]
+
+From the files an IrT stage with train.irt_lights wrote into <dir> (0_irr_texture_light<k>.hdr, the irradiance under inserted emitter k at unit radiance):
+0_irr_texture_lit.hdr = base + sum colour_k * 0_irr_texture_light<k>.hdr -- the listed emitters switched on at those radiances (direct light only).  The
+base is <dir>/0_irr_texture.hdr, or --base <file>, e.g. a 0_irr_texture_relit.hdr from relight-irt.  Irradiance is linear in emitted radiance: nothing is
+traced.  Existing files are not overwritten.
 """
 import sys
 
@@ -189,7 +196,72 @@ def relight_irt(directory, k, colour, replace=False):
     return dst
 
 
+def light_irt(directory, lights, base=None):
+    """lights: [(k, (r, g, b)), ...] -> the path written.  FileExistsError / FileNotFoundError / ValueError name what is wrong"""
+    import os
+    from . import irtlight
+    dst = os.path.join(directory, "0_irr_texture_lit.hdr")
+    if os.path.exists(dst):
+        raise FileExistsError("%s exists: not overwritten" % dst)
+    base = os.path.join(directory, "0_irr_texture.hdr") if base is None else base
+    if not os.path.exists(base):
+        raise FileNotFoundError("no %s: run the IrT stage first, or name the base with --base" % base)
+    if not lights:
+        raise ValueError("light-irt needs at least one --light k --colour r,g,b")
+    E = np.asarray(IO.read_hdr(base), np.float32)
+    F = []
+    for k, _ in lights:
+        f = os.path.join(directory, "0_irr_texture_light%d.hdr" % k)
+        if k < 0 or not os.path.exists(f):
+            raise FileNotFoundError("--light %d needs %s: run the IrT stage with train.irt_lights = <json of the lights>" % (k, f))
+        img = np.asarray(IO.read_hdr(f), np.float32)
+        if img.shape != E.shape:
+            raise ValueError("%s is %r, the base %s is %r" % (f, img.shape, base, E.shape))
+        F.append(img[..., 0])
+    out = irtlight.add(E, np.stack(F), [c for _, c in lights])
+    IO.write_hdr(dst, np.ascontiguousarray(out, np.float32))
+    return dst
+
+
 def main(argv):
+    if len(argv) >= 2 and argv[0] == "light-irt":
+        rest, lights, base, bad = [], [], None, False
+        it = iter(argv[1:])
+        for a in it:
+            key, eq, val = a.partition("=")
+            if key in ("--light", "--colour", "--base"):
+                val = val if eq else next(it, None)
+                try:
+                    if key == "--light":
+                        lights.append([int(val), None])
+                    elif key == "--colour":
+                        colour = tuple(float(v) for v in val.split(","))
+                        if len(colour) != 3 or not lights or lights[-1][1] is not None:
+                            raise ValueError
+                        lights[-1][1] = colour
+                    else:
+                        if val is None or base is not None:
+                            raise ValueError
+                        base = val
+                except (TypeError, ValueError, AttributeError):
+                    bad = True
+            elif a.startswith("--"):
+                bad = True
+            else:
+                rest.append(a)
+        if bad or len(rest) != 1 or not lights or any(c is None for _, c in lights):
+            print("light-irt needs <dir> --light k --colour r,g,b [--light k --colour r,g,b ...] [--base <file>]")
+            return 2
+        try:
+            dst = light_irt(rest[0], [(k, c) for k, c in lights], base)
+        except (FileExistsError, FileNotFoundError) as e:
+            print(e)
+            return 1
+        except ValueError as e:
+            print(e)
+            return 2
+        print("wrote", dst)
+        return 0
     if len(argv) >= 2 and argv[0] == "relight-irt":
         opt, rest, flags = {"--class": None, "--colour": None}, [], []
         it = iter(argv[1:])

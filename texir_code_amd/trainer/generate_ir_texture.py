@@ -89,6 +89,12 @@ class IrrTextureRunner:
                     with phases.phase("write_hdr", sync=False):
                         for k in range(split.shape[0]):
                             IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_%s%d.hdr" % (what, k)), split[k].cpu().numpy())
+            # train.irt_lights (models.TracerO3d): the unit-radiance irradiance of every inserted emitter, its factor in all three channels
+            lights = getattr(self.model, "ir_lights", None)
+            if lights is not None:
+                with phases.phase("write_hdr", sync=False):
+                    for k in range(lights.shape[0]):
+                        IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_light%d.hdr" % k), lights[k][..., None].expand(-1, -1, 3).contiguous().cpu().numpy())
         return irr_texture
 
     def _write_irt(self, irr_texture, path):
