@@ -3,7 +3,8 @@ relight-irt command, on the golden room (20 k triangles, 256^2 texture, a lamp).
 
   1. intervals   every class of `lamp` and `bands` inside the float64 reference of its masked texture (irt_split_cases.split_ref);
   2. equality    bit for bit the existing 64-texel kernel on the masked (unit: indicator) textures: N in 1, 64, 65, 100, 128, 512 and once 2048, every label
-                 image, lists of 130 / 64 / 65 / 1 texels, float-valued (layout 2) and RGBE-born (layout 4) textures;
+                 image, lists of 130 / 64 / 65 / 1 texels, float-valued (layout 2) and RGBE-born (layout 4) textures; two parts of 64 passes and one part
+                 under TEXIR_IRT_MIN_PART_CELLS / TEXIR_IRT_LOG2PARTS;
   3. linearity   combine(E, c) against irt_generate on the recoloured texture, relative L2 <= 1e-3 (the project's parity bound);
   4. purity      shuffled list, three slices, second run, side stream, a captured graph replayed twice: identical bits; sentinels and guard words intact;
   5. errors      every refused argument raises TexirError;
@@ -117,6 +118,15 @@ def test_split_equals_the_64_texel_kernel_on_the_masked_textures(tx, monkeypatch
         K3, bands = SP.labels("bands")
         for (N, n), g in got.items():
             assert np.array_equal(g, split(full, bands, K3, N, ids_of(n))[:2]), (N, n)
+
+
+@pytest.mark.parametrize("N,switch,value,parts", [(128, "TEXIR_IRT_MIN_PART_CELLS", "64", 2), (64, "TEXIR_IRT_LOG2PARTS", "0", 1)])
+def test_split_equals_the_64_texel_kernel_under_the_switches_of_the_plan(tx, monkeypatch, N, switch, value, parts):
+    """the split cuts a texel's passes into the parts irt_plan cuts them into, whatever the switches say: same cells per part, same sums"""
+    from texir_code_amd import _lib
+    monkeypatch.setenv(switch, value)
+    assert int(_lib.lib().texir_irt_split_workspace_bytes(1, N, 3)) == 12 * 3 * parts
+    equal_to_masked_runs(tx, monkeypatch, "float", "bands", False, (N,), (130,))
 
 
 @pytest.mark.parametrize("name", SP.LABEL_NAMES)

@@ -127,6 +127,20 @@ def test_header_declares_and_lib_binds_the_entry_points():
     assert L.texir_irt_split_workspace_bytes(7, 100, 9) == 0 and L.texir_irt_split_workspace_bytes(7, 0, 2) == 0
 
 
+def test_workspace_bytes_follow_the_switches_of_the_plan(monkeypatch):
+    """the split's parts per texel are irt_plan's: the same function of N, TEXIR_IRT_MIN_PART_CELLS and TEXIR_IRT_LOG2PARTS (trace_cases.n_parts restates it)"""
+    from texir_code_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    L = _lib.lib()
+    monkeypatch.setenv("TEXIR_IRT_MIN_PART_CELLS", "64")        # (the fixture calls texir_reload_env after every change, and once more after undoing them)
+    assert TC.n_parts(512, "group", min_part_cells=64) == 8
+    assert L.texir_irt_split_workspace_bytes(130, 512, 3) == 12 * 130 * 3 * TC.n_parts(512, "group", min_part_cells=64)
+    monkeypatch.delenv("TEXIR_IRT_MIN_PART_CELLS")
+    monkeypatch.setenv("TEXIR_IRT_LOG2PARTS", "0")
+    assert L.texir_irt_split_workspace_bytes(130, 512, 3) == 12 * 130 * 3
+
+
 def test_relight_irt_command_on_hand_made_files(tmp_path):
     """values an RGBE file holds exactly (8-bit mantissas under one power of two): the command's arithmetic shows through the files unrounded"""
     from texir_code_amd import io_formats as IO, tools

@@ -1,6 +1,7 @@
 // Device-side building blocks shared by the gfx950 kernels: Hammersley/Cranley-Patterson sampling,
 // local frames, hemisphere/GGX directions (utils/sample_util.py:28-146), per-lane BVH2 traversal
-// with an LDS-resident stack, and the query_irf hit shader (models/tracer_o3d_irt.py:248-267).
+// with an LDS-resident stack and its build configuration, the query_irf hit shader
+// (models/tracer_o3d_irt.py:248-267), the sample order of the multi-texel IrT kernels and wave reductions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,6 +32,35 @@ constexpr int kBlock = 256;          // 4 waves
 constexpr int kLdsStack = 24;        // default: entries per lane kept in LDS (24 KiB per block)
 constexpr int kSentinel = 0x7FFFFFFF;
 constexpr int kStackCap = 96;        // LDS part + private overflow; the host checks the tree's worst case against it
+
+// ------------------------------------------------------------------------------------------------
+// build configuration of the traversal, shared by every tracing kernel (kernels.hip, material.hip, texbake.hip, irtsplit.hip, irtlight.hip)
+// ------------------------------------------------------------------------------------------------
+// Occupancy.  Round 1 (4-byte stack entries): 5 waves / 24 entries 13.85, 6 / 24 14.79, 7 / 16 15.11, 8 / 16 15.06 Grays/s (c4).  Round 2, after the
+// scalar node path took the L1 off the critical path (8-byte entries): 6 waves / 12 entries 15.01, 7 / 11 15.82, 8 / 10 15.87 (c2: 16.30, 17.11, 17.40;
+// c4_scan: 4.98, 5.31, 5.54): 8 waves per SIMD = 64 VGPRs (the compiler parks the per-texel frame and the ray's shear rows in scratch across the
+// traversal loop) and a 10-entry LDS stack.
+#ifndef TEXIR_CULL
+#define TEXIR_CULL 1                                    // stack entries carry the child's entry distance (StackEntry below)
+#endif
+constexpr bool kCull = TEXIR_CULL != 0;
+#ifndef TEXIR_GROUP_LSTK
+#define TEXIR_GROUP_LSTK (TEXIR_CULL ? 10 : 16)         // 8-byte entries with culling: 10 x 2 KiB = 20 KiB per block, 8 blocks = all 160 KiB of a CU
+#endif
+constexpr int kGroupLstk = TEXIR_GROUP_LSTK;            // the IrT kernels (irt_kernel, irt_group_kernel, irt_stream_kernel, irt_split_kernel)
+#ifndef TEXIR_GROUP_WAVES
+#define TEXIR_GROUP_WAVES 8
+#endif
+constexpr int kGroupWaves = TEXIR_GROUP_WAVES;
+constexpr int kLstk = kCull ? kLdsStack / 2 : kLdsStack;   // the single-ray tracing kernels: 24 KiB of stack per block either way
+// which cells a part of a texel's passes holds: 1 = an azimuthal wedge (wedge_cell below), 0 = a ring of elevations
+#ifndef TEXIR_PART_WEDGE
+#define TEXIR_PART_WEDGE 1
+#endif
+// azimuth sine / cosine of the fused IrT sampling from v_sin_f32 / v_cos_f32 (sample_dir<FAST>)
+#ifndef TEXIR_IRT_FAST_SINCOS
+#define TEXIR_IRT_FAST_SINCOS 0
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // sampling -- kept free of fused multiply-adds so that it tracks the reference's separately rounded
@@ -821,6 +851,54 @@ __device__ __forceinline__ float wave_sum(float x)
 {
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
     return x;
+}
+// (counters: a lane's 32-bit count widened before the sum, so the wave's total cannot wrap)
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x)
+{
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// neither inf nor nan
+__device__ __forceinline__ bool finite32(float x) { return x - x == 0.f; }
+
+// ------------------------------------------------------------------------------------------------
+// sample order of the multi-texel IrT kernels (irt_group_kernel, irt_stream_kernel, irt_split_kernel).  A wave traces GRP neighbouring texels at
+// once: lane group g (64/GRP lanes) belongs to texel g and all groups take, in the same pass, the lattice cell of THEIR texel that lies nearest to one
+// absolute direction cell J (cell_to_pass_m).  The 64 rays of a pass then span 1/(32*GRP) of the hemisphere instead of 1/32 (for N = 2048) and start
+// within a few millimetres of each other: their traversals stay together much longer, which is what an issue-bound SIMT traversal needs.
+// Every sample of every texel is still traced exactly once (J -> cell is a bijection for a fixed shift).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t sample_index_m(uint32_t cell, uint32_t sub, int log2N, int log2m)
+{
+    int cells = log2N - log2m;
+    int bphi = (cells + 1) >> 1, bth = cells - bphi;
+    uint32_t low = cell & ((1u << bphi) - 1u);
+    uint32_t th = bth ? (cell >> bphi) : 0u;
+    return (th << (log2N - bth)) | (sub << bphi) | low;
+}
+
+__device__ __forceinline__ uint32_t cell_to_pass_m(uint32_t J, float sh0, float sh1, int log2N, int log2m)
+{
+    int cells = log2N - log2m;
+    int bphi = (cells + 1) >> 1, bth = cells - bphi;
+    uint32_t nphi = 1u << bphi, nth = 1u << bth;
+    uint32_t Jphi = J & (nphi - 1u), Jth = J >> bphi;
+    uint32_t dphi = (uint32_t)(sh1 * (float)nphi + 0.5f), dth = (uint32_t)(sh0 * (float)nth + 0.5f);
+    uint32_t phibin = (Jphi + nphi - (dphi & (nphi - 1u))) & (nphi - 1u);
+    uint32_t th = (Jth + nth - (dth & (nth - 1u))) & (nth - 1u);
+    uint32_t low = bphi ? (__brev(phibin) >> (32 - bphi)) : 0u;
+    return (th << bphi) | low;
+}
+
+// The direction cell J of the Lc-th cell a texel's passes walk; bphi / bth = the azimuth / elevation bits of the cell index.  TEXIR_PART_WEDGE = 1: the
+// cells are walked azimuth-major (all elevations of one azimuth bin, then the next bin), so a part -- a contiguous range of Lc -- is an azimuthal WEDGE of
+// the hemisphere (N = 2048: 2 of the 64 azimuth bins = 5.6 degrees, all 32 elevations) instead of a full ring of one elevation.  The rays of a wedge leave
+// a surface patch towards one side of the room: what they touch deep in the tree, their triangles and their radiance-texture lines are shared by the
+// chunks of neighbouring wedges.  (irt_stream_kernel's `next` keeps this expression as text: see there.)
+__device__ __forceinline__ int wedge_cell(int Lc, int bphi, int bth)
+{
+    return TEXIR_PART_WEDGE ? (((Lc & ((1 << bth) - 1)) << bphi) | (Lc >> bth)) : Lc;
 }
 
 }  // namespace texir

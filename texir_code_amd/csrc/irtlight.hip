@@ -7,7 +7,7 @@
 // coherent a ray bundle as the traversal gets.  A work item is (64-texel group, light); items are dealt statically: wave w of the grid takes items w,
 // w + waves, ... -- no work counter, no wave waits on another, every loop is bounded by K, S, the item count or the traversal's own bounds.  The light record
 // is a wave-uniform (scalar) load; the sample loop runs over i for the whole wave; a sample no lane of the wave needs is skipped by ballot.  Visibility is ONE
-// closest-hit query (device_common.h trace_closest, used as it is, as texbake.hip calls it): occluded iff the closest hit has t < t_max.
+// closest-hit query (device_common.h trace_closest<false, kLstk, WIDTH, kCull>, the single-ray kernels' shared form): occluded iff the closest hit has t < t_max.
 // F is a pure function of the inputs: one float32 accumulator per (texel, light) in ascending i, no atomics on results, no workspace.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,17 +19,7 @@ namespace texir {
 // every product, sum and quotient below is its own rounded float32 operation: the header states the arithmetic and the tests restate it
 #pragma clang fp contract(off)
 
-constexpr bool kLightCull = true;
-constexpr int kLightLstk = kLdsStack / 2;          // 8-byte entries: 24 KiB of traversal stack per block, as the bake keeps
 constexpr float kTwoPi32 = 6.28318548202514648f, kFourPi32 = 12.5663709640502930f;      // the float32 neighbours of 2 pi and 4 pi
-
-__device__ __forceinline__ bool light_finite(float x) { return x - x == 0.f; }
-
-__device__ __forceinline__ unsigned long long light_wave_sum(unsigned long long x)
-{
-    for (int o = 32; o > 0; o >>= 1) x += (unsigned long long)__shfl_xor((long long)x, o, 64);
-    return x;
-}
 
 template <int WIDTH>
 __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm, const float* __restrict__ shift,
@@ -60,17 +50,17 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
         const float cx = L[1], cy = L[2], cz = L[3], ax = L[4], ay = L[5], az = L[6], bx = L[7], by = L[8], bz = L[9];
         const bool quad = kind == 0.f, sphere = kind == 1.f;
         float mx = 0.f, my = 0.f, mz = 0.f, w = 1.f;
-        bool valid = light_finite(cx) && light_finite(cy) && light_finite(cz) && light_finite(ax);
+        bool valid = finite32(cx) && finite32(cy) && finite32(cz) && finite32(ax);
         if (quad) {
             mx = ay * bz - az * by;
             my = az * bx - ax * bz;
             mz = ax * by - ay * bx;
             // (finite m: every word of a and b is finite)
-            valid = valid && light_finite(mx) && light_finite(my) && light_finite(mz) && light_finite(ay) && light_finite(az) && light_finite(bx) && light_finite(by) &&
-                    light_finite(bz) && (mx != 0.f || my != 0.f || mz != 0.f);
+            valid = valid && finite32(mx) && finite32(my) && finite32(mz) && finite32(ay) && finite32(az) && finite32(bx) && finite32(by) &&
+                    finite32(bz) && (mx != 0.f || my != 0.f || mz != 0.f);
         } else if (sphere) {
             w = (kFourPi32 * ax) * ax;
-            valid = valid && ax > 0.f && light_finite(w);
+            valid = valid && ax > 0.f && finite32(w);
         } else valid = false;
 
         float acc = 0.f;
@@ -98,13 +88,13 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
                 float g = 0.f;
                 if (live && nd > 0.f && md > 0.f && dd > 0.f) {
                     g = (nd * md) / (dd * dd);
-                    if (!light_finite(g)) g = 0.f;
+                    if (!finite32(g)) g = 0.f;
                 }
                 const bool need = g > 0.f;
                 if (!__any(need)) continue;                                 // no lane of the wave needs this sample
                 if (need) {
                     it_traced++;
-                    const Hit hit = trace_closest<false, kLightLstk, WIDTH, kLightCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
+                    const Hit hit = trace_closest<false, kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
                     if (!(hit.slot >= 0 && hit.t < t_max)) {
                         it_visible++;
                         acc += g;
@@ -116,22 +106,19 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
         n_traced += it_traced; n_visible += it_visible;
     }
     if (stats) {
-        const unsigned long long a = light_wave_sum(n_traced), b = light_wave_sum(n_visible);
+        const unsigned long long a = wave_sum_u64(n_traced), b = wave_sum_u64(n_visible);
         if (lane == 0) { atomicAdd(stats, a); atomicAdd(stats + 1, b); }
     }
 }
 
 #pragma clang fp contract(fast)
 
-constexpr int kLightMaxBlocks = 2048;     // a fixed cap, as launch_atlas_bake's: nothing is queried per launch (the result does not depend on the grid)
-
 hipError_t launch_irt_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids, int64_t n, int64_t Nt,
                              const float* lights, int K, int S, float t_max, float* F, unsigned long long* stats, hipStream_t st)
 {
     if (n <= 0 || K <= 0) return hipSuccess;
     const int64_t items = ((n + 63) / 64) * K;
-    const int64_t want = (items + (kBlock / 64) - 1) / (kBlock / 64);
-    const int grid = (int)(want < kLightMaxBlocks ? want : kLightMaxBlocks);
+    const int grid = grid_capped(kBlock / 64, items);      // a fixed cap: nothing is queried per launch (the result does not depend on the grid)
     if (sc.nodes4)
         hipLaunchKernelGGL(irt_lights_kernel<4>, dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n, Nt, lights, K, S, t_max, F, stats);
     else

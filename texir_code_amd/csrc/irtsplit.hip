@@ -21,48 +21,15 @@
 
 namespace texir {
 
-// the traversal's template arguments as irt_group_kernel takes them on the 4-wide tree (kernels.hip: kGroupLstk, kCull)
-#ifndef TEXIR_CULL
-#define TEXIR_CULL 1
-#endif
-#ifndef TEXIR_GROUP_LSTK
-#define TEXIR_GROUP_LSTK (TEXIR_CULL ? 10 : 16)
-#endif
-#ifndef TEXIR_IRT_FAST_SINCOS
-#define TEXIR_IRT_FAST_SINCOS 0
-#endif
-constexpr bool kSplitCull = TEXIR_CULL != 0;
-constexpr int kSplitLstk = TEXIR_GROUP_LSTK;
+// (the traversal's template arguments are irt_group_kernel's on the 4-wide tree: device_common.h kGroupLstk, kCull)
 constexpr int kSplitMaxClasses = 8;
 
 // waves per SIMD the kernel is compiled for: 3 accumulators per class on top of irt_group_kernel's 64 registers at 8 waves
 template <int KMAX> struct SplitWaves { static constexpr int value = KMAX <= 2 ? 6 : (KMAX <= 4 ? 5 : 4); };
 
-// sample order of the 64-texel form, restated from kernels.hip (one sample per texel per pass: log2m = 0 there)
-__device__ __forceinline__ uint32_t split_sample_index_m(uint32_t cell, uint32_t sub, int log2N, int log2m)
-{
-    int cells = log2N - log2m;
-    int bphi = (cells + 1) >> 1, bth = cells - bphi;
-    uint32_t low = cell & ((1u << bphi) - 1u);
-    uint32_t th = bth ? (cell >> bphi) : 0u;
-    return (th << (log2N - bth)) | (sub << bphi) | low;
-}
-
-__device__ __forceinline__ uint32_t split_cell_to_pass_m(uint32_t J, float sh0, float sh1, int log2N, int log2m)
-{
-    int cells = log2N - log2m;
-    int bphi = (cells + 1) >> 1, bth = cells - bphi;
-    uint32_t nphi = 1u << bphi, nth = 1u << bth;
-    uint32_t Jphi = J & (nphi - 1u), Jth = J >> bphi;
-    uint32_t dphi = (uint32_t)(sh1 * (float)nphi + 0.5f), dth = (uint32_t)(sh0 * (float)nth + 0.5f);
-    uint32_t phibin = (Jphi + nphi - (dphi & (nphi - 1u))) & (nphi - 1u);
-    uint32_t th = (Jth + nth - (dth & (nth - 1u))) & (nth - 1u);
-    uint32_t low = bphi ? (__brev(phibin) >> (32 - bphi)) : 0u;
-    return (th << bphi) | low;
-}
-
 // ------------------------------------------------------------------------------------------------
 // hit shader: shade_hit's footprint, then one bilinear sum per class -- separately rounded operations, as in device_common.h
+// (split_footprint repeats the first lines of shade_hit; what keeps the two texts equal is the bit-identity tests of tests/test_gpu_irt_split.py)
 // ------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
 
@@ -121,7 +88,7 @@ __global__ __launch_bounds__(kBlock, SplitWaves<KMAX>::value) void irt_split_ker
     const int64_t gw = (int64_t)blockIdx.x * (kBlock / 64) + wave, nw = (int64_t)gridDim.x * (kBlock / 64);
     uint32_t cn = 0, ct = 0;
     const int part_cells = N >> log2parts;
-    // the wedge order of irt_group_kernel: the cells are walked azimuth-major, so a part is an azimuthal wedge of the hemisphere
+    // the cell order of irt_group_kernel with one sample per texel per pass (device_common.h wedge_cell)
     const int cell_bits = log2N < 0 ? 0 : log2N, bphi = (cell_bits + 1) >> 1, bth = cell_bits - bphi;
     const int64_t n_groups = (n_ids + 63) / 64;
     const int64_t n_chunks = n_groups << log2parts;
@@ -138,16 +105,16 @@ __global__ __launch_bounds__(kBlock, SplitWaves<KMAX>::value) void irt_split_ker
 #pragma unroll
         for (int q = 0; q < KMAX; q++) { acc[q][0] = 0.f; acc[q][1] = 0.f; acc[q][2] = 0.f; }
         for (int Lc = part * part_cells; Lc < (part + 1) * part_cells; Lc++) {
-            const int J = log2N >= 0 ? (((Lc & ((1 << bth) - 1)) << bphi) | (Lc >> bth)) : Lc;
+            const int J = log2N >= 0 ? wedge_cell(Lc, bphi, bth) : Lc;
             if (live) {
                 // (N not a power of two: natural sample order)
-                const uint32_t i = log2N < 0 ? (uint32_t)J : split_sample_index_m(split_cell_to_pass_m((uint32_t)J, sh0, sh1, log2N, 0), 0u, log2N, 0);
+                const uint32_t i = log2N < 0 ? (uint32_t)J : sample_index_m(cell_to_pass_m((uint32_t)J, sh0, sh1, log2N, 0), 0u, log2N, 0);
                 float s0 = shift_wrap_clamp(ham0(i, (uint32_t)N), sh0);
                 float s1 = shift_wrap_clamp(ham1(i), sh1);
                 float d[3];
                 sample_dir<TEXIR_IRT_FAST_SINCOS != 0>(mode, s0, s1, 0.f, f, d);
                 const float ndl = fminf(fmaxf(nx * d[0] + ny * d[1] + nz * d[2], 0.f), 1.f);       // :170, RAW normal
-                Hit h = trace_closest<false, kSplitLstk, 4, kSplitCull>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, nullptr);
+                Hit h = trace_closest<false, kGroupLstk, 4, kCull>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, nullptr);
                 if (h.slot >= 0 && h.t > 1e-4f) {          // tracer_o3d_irt.py:248
                     const SplitTaps tp = split_footprint(sc, labels, h.slot, h.u, h.v);
 #pragma unroll
@@ -196,31 +163,13 @@ __global__ __launch_bounds__(256) void irt_split_combine_kernel(const float* __r
 // launcher
 // ------------------------------------------------------------------------------------------------
 
-// parts per texel of the 64-texel plan (kernels.hip irt_plan): a function of N and the two switches alone
-int irt_split_log2parts(int N)
-{
-    if (N <= 0 || (N & (N - 1))) return 0;
-    int l = 0;
-    const int min_cells = env().irt_min_part_cells;
-    while (l < 5 && (N >> (l + 1)) >= min_cells) l++;
-    if (const int cap = env().irt_log2parts_cap; cap >= 0 && l > cap) l = cap;
-    return l;
-}
+// parts per texel of the 64-texel plan, as irt_plan takes them (launch_util.h irt_log2parts)
+static int irt_split_log2parts(int N) { return irt_log2parts(N, env().irt_min_part_cells, env().irt_log2parts_cap); }
 
 size_t irt_split_workspace_bytes(int64_t n_ids, int N, int K)
 {
     if (n_ids <= 0 || N <= 0 || K < 1 || K > kSplitMaxClasses) return 0;
     return (sizeof(float) * 3 * (size_t)n_ids * (size_t)K) << irt_split_log2parts(N);
-}
-
-template <typename Kn>
-static int split_resident_grid(Kn kernel)
-{
-    int dev = 0, cus = 256, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-    return cus * per_cu;
 }
 
 template <int KMAX, bool UNIT>
@@ -229,7 +178,7 @@ static void split_launch(const SceneDev& sc, const float* tex, const uint8_t* la
 {
     const int64_t chunks = ((n_ids + 63) / 64) << log2parts;
     const int64_t want = (chunks + (kBlock / 64) - 1) / (kBlock / 64);
-    int grid = split_resident_grid(irt_split_kernel<KMAX, UNIT>);
+    int grid = resident_grid(irt_split_kernel<KMAX, UNIT>, kBlock);
     if (want < grid) grid = (int)want;
     hipLaunchKernelGGL((irt_split_kernel<KMAX, UNIT>), dim3(grid), dim3(kBlock), 0, st, sc, tex, labels, pos, nrm, shift, ids, n_ids, N, l2, mode, K, partial, log2parts);
 }
@@ -239,8 +188,7 @@ hipError_t launch_irt_split(const SceneDev& sc, const float* tex_row_major, cons
 {
     if (n_ids <= 0) return hipSuccess;
     const bool pow2 = (N & (N - 1)) == 0;
-    int l2 = -1;
-    if (pow2) { l2 = 0; while ((1 << l2) < N) l2++; }
+    const int l2 = pow2 ? ilog2_exact(N) : -1;
     const int log2parts = irt_split_log2parts(N);
 #define TEXIR_SPLIT(KMAX) { if (unit) split_launch<KMAX, true>(sc, tex_row_major, labels, pos, nrm, shift, ids, n_ids, N, l2, mode, K, partial, log2parts, st); \
                             else split_launch<KMAX, false>(sc, tex_row_major, labels, pos, nrm, shift, ids, n_ids, N, l2, mode, K, partial, log2parts, st); }
@@ -250,9 +198,7 @@ hipError_t launch_irt_split(const SceneDev& sc, const float* tex_row_major, cons
 #undef TEXIR_SPLIT
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    int64_t blocks = (3 * n_ids * K + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(irt_split_combine_kernel, dim3((int)blocks), dim3(256), 0, st, partial, ids, n_ids, Nt, K, 1 << log2parts, N, 2.f, out);
+    hipLaunchKernelGGL(irt_split_combine_kernel, dim3(grid_capped(256, 3 * n_ids * K)), dim3(256), 0, st, partial, ids, n_ids, Nt, K, 1 << log2parts, N, 2.f, out);
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "device_common.h"
+#include "launch_util.h"
 
 namespace texir {
 hipError_t launch_irt(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids, int64_t n_ids,

@@ -14,8 +14,6 @@
 
 namespace texir {
 
-static int grid_for_static(int64_t per_block, int64_t n) { int64_t w = (n + per_block - 1) / per_block; return (int)(w < 1 ? 1 : (w > 2048 ? 2048 : w)); }
-
 // Sample order inside a texel.  The estimator is a plain sum, so the order is free; choose it so that the 64
 // samples a wave traces together fall into one (phi-bin, cos-theta-bin) cell of the Hammersley lattice
 // (i's low bits are phi's high bits after the radical inverse; i's high bits are theta).  Coherent rays share
@@ -37,8 +35,7 @@ __device__ __forceinline__ void irt_stats_flush(unsigned long long* stats, int l
 {
     uint32_t v[8] = {rays, nodes, tris, hits, wi[0], wi[1], wi[kWiCulled], wi[kWiOverflow]};
     for (int q = 0; q < 8; q++) {
-        unsigned long long x = v[q];
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+        const unsigned long long x = wave_sum_u64(v[q]);
         if (lane == 0 && x) atomicAdd(&stats[q], x);
     }
 }
@@ -55,34 +52,11 @@ __device__ __forceinline__ void irt_probe_flush(unsigned long long* stats, int l
 }
 #endif
 
-// Occupancy.  Round 1 (4-byte stack entries): 5 waves / 24 entries 13.85, 6 / 24 14.79, 7 / 16 15.11, 8 / 16 15.06 Grays/s (c4).  Round 2, after the
-// scalar node path took the L1 off the critical path (8-byte entries): 6 waves / 12 entries 15.01, 7 / 11 15.82, 8 / 10 15.87 (c2: 16.30, 17.11, 17.40;
-// c4_scan: 4.98, 5.31, 5.54): 8 waves per SIMD = 64 VGPRs (the compiler parks the per-texel frame and the ray's shear rows in scratch across the
-// traversal loop) and a 10-entry LDS stack.
-#ifndef TEXIR_CULL
-#define TEXIR_CULL 1
-#endif
-constexpr bool kCull = TEXIR_CULL != 0;
 constexpr int kEstimatorCosine = 4;      // or-ed into the IrT kernels' `mode`: the cosine branch of diffuse_reflectance (mat_nvdiffrast.py:256-257)
-#ifndef TEXIR_GROUP_LSTK
-#define TEXIR_GROUP_LSTK (TEXIR_CULL ? 10 : 16)         // 8-byte entries with culling: 10 x 2 KiB = 20 KiB per block, 8 blocks = all 160 KiB of a CU
-#endif
-constexpr int kGroupLstk = TEXIR_GROUP_LSTK;
-#ifndef TEXIR_GROUP_WAVES
-#define TEXIR_GROUP_WAVES 8
-#endif
-constexpr int kGroupWaves = TEXIR_GROUP_WAVES;
-constexpr int kLstk = kCull ? kLdsStack / 2 : kLdsStack;   // the other tracing kernels: 24 KiB of stack per block either way
+// (occupancy and stack sizes of the kernels below: device_common.h kGroupWaves, kGroupLstk, kLstk, kCull)
 // chunk hand-out of irt_group_kernel (see there): 0 = one counter, parts = elevation rings (round 2)
 #ifndef TEXIR_XCD_SCHED
 #define TEXIR_XCD_SCHED 1
-#endif
-#ifndef TEXIR_PART_WEDGE
-#define TEXIR_PART_WEDGE 1
-#endif
-// azimuth sine / cosine of the fused IrT sampling from v_sin_f32 / v_cos_f32 (device_common.h sample_dir<FAST>)
-#ifndef TEXIR_IRT_FAST_SINCOS
-#define TEXIR_IRT_FAST_SINCOS 0
 #endif
 
 // One texel per wave: the 64 lanes trace 64 samples of the texel per pass (any N, binary or 4-wide tree).  Kept as the
@@ -137,33 +111,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_kernel(SceneDev sc, c
     if (STATS) irt_stats_flush(stats, lane, c_rays, c_nodes, c_tris, c_hits, wi);
 }
 
-// Multi-texel passes.  A wave traces GRP neighbouring texels at once: lane group g (64/GRP lanes) belongs to texel g and all groups
-// take, in the same pass, the lattice cell of THEIR texel that lies nearest to one absolute direction cell J (cell_to_pass_m).
-// The 64 rays of a pass then span 1/(32*GRP) of the hemisphere instead of 1/32 (for N = 2048) and start within a few
-// millimetres of each other: their traversals stay together much longer, which is what an issue-bound SIMT traversal needs.
-// Every sample of every texel is still traced exactly once (J -> cell is a bijection for a fixed shift).
-__device__ __forceinline__ uint32_t sample_index_m(uint32_t cell, uint32_t sub, int log2N, int log2m)
-{
-    int cells = log2N - log2m;
-    int bphi = (cells + 1) >> 1, bth = cells - bphi;
-    uint32_t low = cell & ((1u << bphi) - 1u);
-    uint32_t th = bth ? (cell >> bphi) : 0u;
-    return (th << (log2N - bth)) | (sub << bphi) | low;
-}
-
-__device__ __forceinline__ uint32_t cell_to_pass_m(uint32_t J, float sh0, float sh1, int log2N, int log2m)
-{
-    int cells = log2N - log2m;
-    int bphi = (cells + 1) >> 1, bth = cells - bphi;
-    uint32_t nphi = 1u << bphi, nth = 1u << bth;
-    uint32_t Jphi = J & (nphi - 1u), Jth = J >> bphi;
-    uint32_t dphi = (uint32_t)(sh1 * (float)nphi + 0.5f), dth = (uint32_t)(sh0 * (float)nth + 0.5f);
-    uint32_t phibin = (Jphi + nphi - (dphi & (nphi - 1u))) & (nphi - 1u);
-    uint32_t th = (Jth + nth - (dth & (nth - 1u))) & (nth - 1u);
-    uint32_t low = bphi ? (__brev(phibin) >> (32 - bphi)) : 0u;
-    return (th << bphi) | low;
-}
-
+// Multi-texel passes: GRP neighbouring texels per wave, all taking the same absolute direction cell in a pass (device_common.h sample_index_m, cell_to_pass_m).
 template <bool STATS, int WIDTH, int LOG2GRP>
 __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm,
                                                            const float* __restrict__ shift, const int32_t* __restrict__ ids, int64_t n_ids,
@@ -181,10 +129,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
     // A chunk = GRP texels x (all passes / 2^log2parts).  With parts > 1 the raw partial sums go to partial[part][k][3] and
     // irt_combine_kernel adds them in part order: the result depends on N only, never on how the texel list is cut or scheduled.
     const int part_cells = n_cells >> log2parts;
-    // Which cells a part holds (TEXIR_PART_WEDGE = 1): the cells are walked azimuth-major (all elevations of one azimuth bin, then the next
-    // bin), so a part is an azimuthal WEDGE of the hemisphere (N = 2048: 2 of the 64 azimuth bins = 5.6 degrees, all 32 elevations) instead of a
-    // full ring of one elevation.  The rays of a wedge leave a surface patch towards one side of the room: what they touch deep in the tree,
-    // their triangles and their radiance-texture lines are shared by the chunks of neighbouring wedges -- which the hand-out below keeps on one XCD.
+    // Which cells a part holds: an azimuthal wedge of the hemisphere (device_common.h wedge_cell); the hand-out below keeps neighbouring wedges on one XCD.
     const int cell_bits = log2N < 0 ? 0 : log2N - LOG2M, bphi = (cell_bits + 1) >> 1, bth = cell_bits - bphi;
     // XCD-aware hand-out (TEXIR_XCD_SCHED = 1): the 8 XCDs have private 4 MiB L2s; with ONE chunk counter consecutive chunks -- the 32 parts of the
     // same 64 texels -- go to whichever waves ask next, so every L2 sees every direction of every region.  Here each XCD owns parts / 8
@@ -225,7 +170,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
         const Frame f = make_frame(nx, ny, nz);
         float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
         for (int Lc = part * part_cells; Lc < (part + 1) * part_cells; Lc++) {
-            const int J = (TEXIR_PART_WEDGE && log2N >= 0) ? (((Lc & ((1 << bth) - 1)) << bphi) | (Lc >> bth)) : Lc;
+            const int J = log2N >= 0 ? wedge_cell(Lc, bphi, bth) : Lc;
 #if TEXIR_CHAIN_PROBE
             const bool pass_timed = (Lc & 7) == 0;
             uint32_t pass_c0 = 0;
@@ -358,7 +303,7 @@ __global__ __launch_bounds__(kBlock, TEXIR_STREAM_WAVES) void irt_stream_kernel(
                     if (STATS) c_hits++;
                 }
                 if (Lc >= Lend) return false;
-                const int J = TEXIR_PART_WEDGE ? (((Lc & ((1 << bth) - 1)) << bphi) | (Lc >> bth)) : Lc;
+                const int J = TEXIR_PART_WEDGE ? (((Lc & ((1 << bth) - 1)) << bphi) | (Lc >> bth)) : Lc;      // device_common.h wedge_cell, as text: the call re-schedules this lambda
                 Lc++;
                 Frame f;
                 for (int a = 0; a < 3; a++) { f.n[a] = keep[a]; f.U[a] = keep[3 + a]; f.V[a] = keep[6 + a]; }
@@ -472,7 +417,7 @@ hipError_t launch_tex_pack(const float* src, uint32_t* dst, int Ht, int Wt, int 
     if (!bytes) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned int), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(tex_pack_kernel, dim3(grid_for_static(256, (int64_t)(bytes / 4))), dim3(256), 0, st, src, dst, Ht, Wt, layout, tx, ty, bad);
+    hipLaunchKernelGGL(tex_pack_kernel, dim3(grid_capped(256, (int64_t)(bytes / 4))), dim3(256), 0, st, src, dst, Ht, Wt, layout, tx, ty, bad);
     return hipGetLastError();
 }
 
@@ -505,7 +450,7 @@ hipError_t launch_tex_retile(const float* src, float* dst, int Ht, int Wt, int l
     int tx, ty;
     const size_t bytes = tex_retile_bytes(Ht, Wt, layout, &tx, &ty);
     if (!bytes) return hipSuccess;
-    hipLaunchKernelGGL(tex_retile_kernel, dim3(grid_for_static(256, (int64_t)(bytes / 4))), dim3(256), 0, st, src, dst, Ht, Wt, layout, tx, ty);
+    hipLaunchKernelGGL(tex_retile_kernel, dim3(grid_capped(256, (int64_t)(bytes / 4))), dim3(256), 0, st, src, dst, Ht, Wt, layout, tx, ty);
     return hipGetLastError();
 }
 
@@ -749,27 +694,6 @@ __global__ __launch_bounds__(kBlock) void spec_bwd_ws_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static int grid_for(int64_t work_items_per_block_unit, int64_t n)
-{
-    // >> 256 workgroups to fill 256 CUs x several blocks/CU; persistent grid-stride above that
-    int64_t want = (n + work_items_per_block_unit - 1) / work_items_per_block_unit;
-    int64_t cap = 256 * 8;
-    return (int)(want < 1 ? 1 : (want > cap ? cap : want));
-}
-
-static int ilog2_exact(int N) { if (N <= 0 || (N & (N - 1))) return 0; int l = 0; while ((1 << l) < N) l++; return l; }
-
-// workgroups that are co-resident on the whole chip for a kernel (so a grid-stride loop has no second, partial round)
-template <typename K>
-static int resident_grid(K kernel, int block)
-{
-    int dev = 0, cus = 256, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-    return cus * per_cu;
-}
-
 // TEXIR_IRT_TEXELS_PER_WAVE = 1 | 64 forces the kernel form (A/B measurements, parity tests of each form); unset or 0 = automatic (env.h).
 static int irt_forced_texels_per_wave() { return env().irt_texels_per_wave; }
 
@@ -787,12 +711,8 @@ IrtPlan irt_plan(const SceneDev& sc, int64_t n_ids, int N)
     const bool pow2 = (N & (N - 1)) == 0;
     p.width = sc.nodes4 ? 4 : 2;
     p.per_wave = !sc.nodes4 ? 1 : (forced ? forced : (n_ids >= 32768 ? 64 : 1));
-    p.log2parts = 0;
-    // parts per texel: up to 32, down to 8 passes per part (N = 2048: 32 parts of 64 passes; N = 64 -- the reference's own configuration -- 8 parts of 8:
-    // with 64-pass parts its 3 053 chunks left two thirds of the 8 192 resident waves without work).  A function of N alone.
-    const int min_cells = env().irt_min_part_cells;                                                                      // A/B switch (default 8; round 2: 64)
-    if (sc.nodes4 && p.per_wave == 64 && pow2) { while (p.log2parts < 5 && (N >> (p.log2parts + 1)) >= min_cells) p.log2parts++; }
-    if (const int cap = env().irt_log2parts_cap; cap >= 0 && p.log2parts > cap) p.log2parts = cap;                        // A/B switch
+    // parts per texel (launch_util.h irt_log2parts; A/B switches: min_part_cells default 8, round 2: 64; log2parts_cap)
+    p.log2parts = sc.nodes4 && p.per_wave == 64 ? irt_log2parts(N, env().irt_min_part_cells, env().irt_log2parts_cap) : 0;
     const bool stream = p.per_wave == 64 && env().irt_refill && pow2 && p.log2parts > 0;
     if (stream) snprintf(p.name, sizeof(p.name), "irt_stream_kernel<false, %d>", p.width);
     else snprintf(p.name, sizeof(p.name), p.per_wave == 64 ? "irt_group_kernel<false, %d, 6>" : "irt_kernel<false, %d>", p.width);
@@ -874,7 +794,7 @@ hipError_t launch_irt(const SceneDev& sc, const float* pos, const float* nrm, co
     else TEXIR_IRT(((n_ids + 63) / 64) << log2parts, pow2 ? l2 : -1, irt_group_kernel, 4, 6)   // any N (natural sample order if not 2^k)
 #undef TEXIR_IRT
     if (log2parts) {
-        hipLaunchKernelGGL(irt_combine_kernel, dim3(grid_for(256, 3 * n_ids)), dim3(256), 0, st, partial, ids, n_ids, 1 << log2parts, N, (mode & kEstimatorCosine) ? 1.f : 2.f, irr);
+        hipLaunchKernelGGL(irt_combine_kernel, dim3(grid_capped(256, 3 * n_ids)), dim3(256), 0, st, partial, ids, n_ids, 1 << log2parts, N, (mode & kEstimatorCosine) ? 1.f : 2.f, irr);
         if (!scratch && (e = hipFreeAsync(partial, st)) != hipSuccess) return e;
     }
     return hipGetLastError();
@@ -890,8 +810,7 @@ hipError_t irt_probe_node_utilisation(const SceneDev& sc, const float* pos, cons
     if (!sc.nodes4 || !ids || count < 64 || (N & (N - 1))) return hipSuccess;
     const int Nc = N > 256 ? 256 : N;
     const int l2 = ilog2_exact(Nc);
-    int log2parts = 0;
-    while (log2parts < 5 && (Nc >> (log2parts + 1)) >= 8) log2parts++;
+    const int log2parts = irt_log2parts(Nc, 8);
     if (!log2parts) return hipSuccess;
     hipError_t e;
     float* partial = nullptr; unsigned long long* stats = nullptr;
@@ -918,15 +837,15 @@ hipError_t launch_trace_shade(const SceneDev& sc, const float* org, const float*
                               uint32_t* prim, float* puv, hipStream_t st)
 {
     if (R <= 0) return hipSuccess;
-    if (sc.nodes4) hipLaunchKernelGGL(trace_shade_kernel<4>, dim3(grid_for(kBlock, R)), dim3(kBlock), 0, st, sc, org, dir, R, t_min, rad, t_hit, prim, puv);
-    else hipLaunchKernelGGL(trace_shade_kernel<2>, dim3(grid_for(kBlock, R)), dim3(kBlock), 0, st, sc, org, dir, R, t_min, rad, t_hit, prim, puv);
+    if (sc.nodes4) hipLaunchKernelGGL(trace_shade_kernel<4>, dim3(grid_capped(kBlock, R)), dim3(kBlock), 0, st, sc, org, dir, R, t_min, rad, t_hit, prim, puv);
+    else hipLaunchKernelGGL(trace_shade_kernel<2>, dim3(grid_capped(kBlock, R)), dim3(kBlock), 0, st, sc, org, dir, R, t_min, rad, t_hit, prim, puv);
     return hipGetLastError();
 }
 
 hipError_t launch_gen_dir(const float* normals, const float* rough, const float* shift, int64_t b, int N, int mode, float* L, hipStream_t st)
 {
     if (b <= 0 || N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gen_dir_kernel, dim3(grid_for(256, b * (int64_t)N)), dim3(256), 0, st, normals, rough, shift, b, N, mode, L);
+    hipLaunchKernelGGL(gen_dir_kernel, dim3(grid_capped(256, b * (int64_t)N)), dim3(256), 0, st, normals, rough, shift, b, N, mode, L);
     return hipGetLastError();
 }
 

@@ -373,8 +373,7 @@ hipError_t launch_loss(int stage, int l2, const float* gt, const float* rgb, con
     hipLaunchKernelGGL(loss_clear_kernel, dim3(1), dim3(kLB), 0, st, (uint32_t*)workspace, (int)(head / 4));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    int64_t nb = (P + kLB - 1) / kLB;
-    int grid = (int)(nb > 2048 ? 2048 : (nb < 1 ? 1 : nb));
+    const int grid = grid_capped(kLB, P);
     size_t lds_stats = sizeof(double) * rc * 4;
     if (lds_stats > 60000) return hipErrorInvalidValue;     // R*C too large for the per-block LDS accumulators
     LossArgs a{gt, rgb, albedo, rough, empty, gtm, seg, hl, room, P, C, R > 0 ? R : 1, hw, stage, l2, d_rgb, d_albedo, d_rough};

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void gbuffer_kernel(SceneDev sc, GbufArgs g
         const float s2 = 2.f / (float)g.c;
         float dXx = s2 * fb.dx[0], dXy = s2 * fb.dx[1], dXz = s2 * fb.dx[2];
         float dYx = s2 * fb.dy[0], dYy = s2 * fb.dy[1], dYz = s2 * fb.dy[2];
-        Hit h = trace_closest<false, kLdsStack / 2, WIDTH, true>(sc, ex, ey, ez, dx, dy, dz, cn, ct);
+        Hit h = trace_closest<false, kLstk, WIDTH, kCull>(sc, ex, ey, ez, dx, dy, dz, cn, ct);
         float o_pos[3] = {1.f, 0.f, 0.f}, o_n[3] = {1.f, 0.f, 0.f}, o_uv[2] = {0.f, 0.f}, o_da[4] = {0.f, 0.f, 0.f, 0.f};   // bg (mat_nvdiffrast.py:125)
         float m = 0.f; int32_t tri = 0;
         if (h.slot >= 0) {
@@ -144,10 +144,9 @@ hipError_t launch_gbuffer(const SceneDev& sc, const float* mvp_host, const float
         if (len > 0.0) for (int k = 0; k < 3; k++) { g.face[f].d0[k] = (float)(g.face[f].d0[k] / len); g.face[f].dx[k] = (float)(g.face[f].dx[k] / len); g.face[f].dy[k] = (float)(g.face[f].dy[k] / len); }
     }
     g.cnrm = cnrm; g.c = c; g.flip_v = flip_v; g.pos = pos; g.nrm = nrm; g.mask = mask; g.uv = uv; g.uvda = uvda; g.tri = tri;
-    int64_t P = (int64_t)6 * c * c;
-    int64_t nb = (P + kBlock - 1) / kBlock;
-    if (sc.nodes4) hipLaunchKernelGGL(gbuffer_kernel<4>, dim3((int)(nb > 2048 ? 2048 : nb)), dim3(kBlock), 0, st, sc, g);
-    else hipLaunchKernelGGL(gbuffer_kernel<2>, dim3((int)(nb > 2048 ? 2048 : nb)), dim3(kBlock), 0, st, sc, g);
+    const dim3 grid(grid_capped(kBlock, (int64_t)6 * c * c));
+    if (sc.nodes4) hipLaunchKernelGGL(gbuffer_kernel<4>, grid, dim3(kBlock), 0, st, sc, g);
+    else hipLaunchKernelGGL(gbuffer_kernel<2>, grid, dim3(kBlock), 0, st, sc, g);
     return hipGetLastError();
 }
 
@@ -565,8 +564,6 @@ __global__ __launch_bounds__(256) void tex_fetch_kernel(float* __restrict__ lvl0
     tex_fetch_body<BWD>(lvl0, rest, d, uv, uvda, trilinear, P, io, blockIdx.x, gridDim.x);
 }
 
-static int grid1d(int64_t n, int bs) { int64_t nb = (n + bs - 1) / bs; return (int)(nb > 4096 ? 4096 : (nb < 1 ? 1 : nb)); }
-
 constexpr int kTailElems = 16 * 16 * 4;     // levels with at most this many elements are handled by the single-block tail kernels (measured: 64^2 1.36, 32^2 1.31, 16^2 1.29, 8^2 1.29, none 1.31 ms per material step)
 
 static int tail_begin(const MipDesc& d)
@@ -732,7 +729,7 @@ hipError_t launch_tex_taps(int H, int W, int C, int levels, const float* uv, con
 {
     if (P <= 0) return hipSuccess;
     MipDesc d = make_desc(H, W, C, levels);
-    hipLaunchKernelGGL(tex_taps_kernel, dim3(grid1d(P, 256)), dim3(256), 0, st, d, uv, uvda, trilinear, P, keys, weights);
+    hipLaunchKernelGGL(tex_taps_kernel, dim3(grid_capped(256, P, 4096)), dim3(256), 0, st, d, uv, uvda, trilinear, P, keys, weights);
     return hipGetLastError();
 }
 
@@ -746,7 +743,7 @@ hipError_t launch_tex_gather_bwd(float* d_tex, float* grad_rest, int H, int W, i
     MipDesc d = make_desc(H, W, C, levels);
     const int64_t n0 = (int64_t)H * W;
     if (n_seg > 0) {
-        dim3 grid(grid1d(n_seg, 256));
+        dim3 grid(grid_capped(256, n_seg, 4096));
         if (C == 1) hipLaunchKernelGGL(tex_gather_kernel<1>, grid, dim3(256), 0, st, d_tex, grad_rest, n0, seg_key, seg_start, seg_count, n_seg, pix, w, d_out);
         else if (C == 2) hipLaunchKernelGGL(tex_gather_kernel<2>, grid, dim3(256), 0, st, d_tex, grad_rest, n0, seg_key, seg_start, seg_count, n_seg, pix, w, d_out);
         else if (C == 3) hipLaunchKernelGGL(tex_gather_kernel<3>, grid, dim3(256), 0, st, d_tex, grad_rest, n0, seg_key, seg_start, seg_count, n_seg, pix, w, d_out);
@@ -761,7 +758,7 @@ hipError_t launch_tex_fetch(const float* tex, const float* rest, int H, int W, i
 {
     if (P <= 0) return hipSuccess;
     MipDesc d = make_desc(H, W, C, levels);
-    hipLaunchKernelGGL(tex_fetch_kernel<false>, dim3(grid1d(P, 256)), dim3(256), 0, st, const_cast<float*>(tex), const_cast<float*>(rest), d, uv, uvda,
+    hipLaunchKernelGGL(tex_fetch_kernel<false>, dim3(grid_capped(256, P, 4096)), dim3(256), 0, st, const_cast<float*>(tex), const_cast<float*>(rest), d, uv, uvda,
                        trilinear, P, out);
     return hipGetLastError();
 }
@@ -772,7 +769,7 @@ hipError_t launch_tex_fetch_bwd(float* d_tex, float* grad_rest, int H, int W, in
 {
     MipDesc d = make_desc(H, W, C, levels);
     if (P > 0)
-        hipLaunchKernelGGL(tex_fetch_kernel<true>, dim3(grid1d(P, 256)), dim3(256), 0, st, d_tex, grad_rest, d, uv, uvda, trilinear, P, const_cast<float*>(d_out));
+        hipLaunchKernelGGL(tex_fetch_kernel<true>, dim3(grid_capped(256, P, 4096)), dim3(256), 0, st, d_tex, grad_rest, d, uv, uvda, trilinear, P, const_cast<float*>(d_out));
     if (trilinear && levels > 1) launch_folds(d_tex, grad_rest, d, H, W, C, levels, fold_to_level, st);
     return hipGetLastError();
 }
@@ -1090,7 +1087,7 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, 
         step_size = (float)((double)lr / bc1);
         bc2_sqrt = (float)sqrt(bc2);
     }
-    hipLaunchKernelGGL(adam_kernel, dim3(grid1d(n, 256 * 4)), dim3(256), 0, st, p, g, m, v, n, beta1, beta2, eps, step_size, bc2_sqrt, lo, hi, hyp);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_capped(256 * 4, n, 4096)), dim3(256), 0, st, p, g, m, v, n, beta1, beta2, eps, step_size, bc2_sqrt, lo, hi, hyp);
     return hipGetLastError();
 }
 
@@ -1248,7 +1245,7 @@ int texir_grad_add_masked(float* g, const float* g0, const uint32_t* mask, int64
     if (n_texels < 0 || C < 1 || C > 4) return bfail(TEXIR_ERR_INVALID, "%s: bad size n_texels=%lld C=%d", fn, (long long)n_texels, (int)C);
     if (n_texels == 0) return TEXIR_OK;
     if (!g || !g0 || !mask) return bfail(TEXIR_ERR_INVALID, "%s: null argument", fn);
-    hipLaunchKernelGGL(grad_add_masked_kernel, dim3(grid1d(n_texels * C, 256 * 4)), dim3(256), 0, (hipStream_t)stream, g, g0, mask, (int64_t)n_texels, (int)C);
+    hipLaunchKernelGGL(grad_add_masked_kernel, dim3(grid_capped(256 * 4, n_texels * C, 4096)), dim3(256), 0, (hipStream_t)stream, g, g0, mask, (int64_t)n_texels, (int)C);
     BATCH_HIP_TRY(fn, hipGetLastError());
     return TEXIR_OK;
 }
@@ -1303,7 +1300,7 @@ int texir_tex_fetch_forward_batch(const texir_tex_fetch_job* jobs, int32_t n, vo
         if (q.P <= 0) continue;
         FetchJob& J = fb.j[fb.n++];
         J.lvl0 = const_cast<float*>(q.tex); J.rest = q.mips_rest; J.d = make_desc(q.H, q.W, q.C, q.levels); J.uv = q.uv; J.uvda = q.uv_da; J.trilinear = q.filter_mode; J.P = q.P; J.out = q.out;
-        J.first = blocks; J.nb = grid1d(q.P, 256);
+        J.first = blocks; J.nb = grid_capped(256, q.P, 4096);
         blocks += J.nb;
     }
     if (fb.n > 0) hipLaunchKernelGGL(tex_fetch_batch_kernel, dim3(blocks), dim3(256), 0, st, fb);
@@ -1344,7 +1341,7 @@ int texir_tex_gather_backward_batch(const texir_tex_gather_job* jobs, int32_t n,
         if (q.n_seg <= 0) continue;
         GatherJob& J = gb.j[gb.n++];
         J.lvl0 = q.d_tex; J.rest = q.grad_rest; J.n0 = (int64_t)q.H * q.W; J.seg_key = (const long long*)q.seg_key; J.seg_start = q.seg_start; J.seg_count = q.seg_count; J.n_seg = q.n_seg;
-        J.pix = q.pix; J.w = q.weights; J.d_out = q.d_out; J.d_out2 = q.d_out2; J.C = q.C; J.first = blocks; J.nb = grid1d(q.n_seg, 256);
+        J.pix = q.pix; J.w = q.weights; J.d_out = q.d_out; J.d_out2 = q.d_out2; J.C = q.C; J.first = blocks; J.nb = grid_capped(256, q.n_seg, 4096);
         blocks += J.nb;
     }
     if (gb.n > 0) hipLaunchKernelGGL(tex_gather_batch_kernel, dim3(blocks), dim3(256), 0, st, gb);

@@ -8,7 +8,7 @@
 // bundle the traversal gets).  The views are walked in ascending order by the whole wave; the view's matrix and position are wave-uniform (scalar) loads.
 // A lane traces a view only when it faces it, its pixel is valid and its score beats the lane's best so far (views come in ascending order, so a tie never
 // replaces an earlier view: the lowest id keeps it); a view no lane of the wave needs is skipped by ballot.  The segment test is ONE closest-hit query
-// (device_common.h trace_closest, used as it is) with org = pos, dir = camera - pos: the view is occluded iff the closest hit has t < 1.
+// (device_common.h trace_closest<false, kLstk, WIDTH, kCull>, the single-ray kernels' shared form) with org = pos, dir = camera - pos: the view is occluded iff the closest hit has t < 1.
 // The outcome per texel is a pure function of the inputs: no atomics on results, nothing depends on the list's order or the launch shape.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,8 +20,6 @@ namespace texir {
 // every product, sum and quotient below is its own rounded float32 operation: the header states the arithmetic and the tests restate it
 #pragma clang fp contract(off)
 
-constexpr bool kBakeCull = true;
-constexpr int kBakeLstk = kLdsStack / 2;          // 8-byte entries: 24 KiB of traversal stack per block, as the other single-ray tracing kernels keep
 constexpr float kPi32 = 3.14159274101257324f, kHalfPi32 = 1.57079637050628662f;
 
 // the pixel rule: t = W (p, 1) -> (row, col) of an h x w equirectangular panorama; false when |t| is zero or not finite
@@ -31,7 +29,7 @@ __device__ __forceinline__ bool pano_pixel(const float* __restrict__ Wm, float p
     const float ty = ((Wm[4] * px + Wm[5] * py) + Wm[6] * pz) + Wm[7];
     const float tz = ((Wm[8] * px + Wm[9] * py) + Wm[10] * pz) + Wm[11];
     const float r2 = (tx * tx + ty * ty) + tz * tz;
-    if (!(r2 > 0.f) || !(r2 - r2 == 0.f)) return false;
+    if (!(r2 > 0.f) || !finite32(r2)) return false;
     const float r = sqrtf(r2);
     const float az = atan2f(tx, tz);
     const float q = fminf(fmaxf(ty / r, -1.f), 1.f);
@@ -41,12 +39,6 @@ __device__ __forceinline__ bool pano_pixel(const float* __restrict__ Wm, float p
     col = (int)fminf(fmaxf(floorf(x), 0.f), (float)(w - 1));
     row = (int)fminf(fmaxf(floorf(y), 0.f), (float)(h - 1));
     return true;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u32(uint32_t x)
-{
-    for (int o = 32; o > 0; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o, 64);
-    return (unsigned long long)x;
 }
 
 template <int WIDTH>
@@ -90,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void atlas_bake_kernel(SceneDev sc, const f
             if (!__any(need)) continue;                                    // no lane of the wave needs this view
             if (need) {
                 n_traced++;
-                const Hit hit = trace_closest<false, kBakeLstk, WIDTH, kBakeCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
+                const Hit hit = trace_closest<false, kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
                 if (!(hit.slot >= 0 && hit.t < 1.f)) {
                     n_visible++;
                     best_k = k; best_s = s; best_row = row; best_col = col;
@@ -110,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void atlas_bake_kernel(SceneDev sc, const f
         }
     }
     if (stats) {
-        const unsigned long long a = wave_sum_u32(n_facing), b = wave_sum_u32(n_traced), c = wave_sum_u32(n_visible), d = wave_sum_u32(n_assigned);
+        const unsigned long long a = wave_sum_u64(n_facing), b = wave_sum_u64(n_traced), c = wave_sum_u64(n_visible), d = wave_sum_u64(n_assigned);
         if ((threadIdx.x & 63) == 0) {
             atomicAdd(stats, a); atomicAdd(stats + 1, b); atomicAdd(stats + 2, c); atomicAdd(stats + 3, d);
         }
@@ -131,18 +123,12 @@ __global__ __launch_bounds__(256) void atlas_gather_kernel(const int32_t* __rest
     }
 }
 
-static int bake_grid(int64_t per_block, int64_t n)
-{
-    const int64_t want = (n + per_block - 1) / per_block;
-    return (int)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-}
-
 hipError_t launch_atlas_bake(const SceneDev& sc, const float* pos, const float* nrm, const int32_t* ids, int64_t n, int64_t Nt, const float* cams, const float* cam_pos,
                              const float* panos, const uint8_t* valid, int K, int h, int w, float cos_min, int32_t* view, int32_t* pix, float* rgb,
                              unsigned long long* stats, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    const dim3 grid(bake_grid(kBlock, n));
+    const dim3 grid(grid_capped(kBlock, n));
     if (sc.nodes4)
         hipLaunchKernelGGL(atlas_bake_kernel<4>, grid, dim3(kBlock), 0, st, sc, pos, nrm, ids, n, Nt, cams, cam_pos, (const uint32_t*)panos, valid, K, h, w, cos_min,
                            view, pix, (uint32_t*)rgb, stats);
@@ -156,7 +142,7 @@ hipError_t launch_atlas_gather(const int32_t* view, const int32_t* pix, const in
                                float* out, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(atlas_gather_kernel, dim3(bake_grid(256, n)), dim3(256), 0, st, view, pix, ids, n, Nt, (const uint32_t*)imgs, K, h, w, C, (uint32_t*)out);
+    hipLaunchKernelGGL(atlas_gather_kernel, dim3(grid_capped(256, n)), dim3(256), 0, st, view, pix, ids, n, Nt, (const uint32_t*)imgs, K, h, w, C, (uint32_t*)out);
     return hipGetLastError();
 }
 

@@ -216,11 +216,6 @@ __device__ __forceinline__ float wave_max_f(float x)
     for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
     return x;
 }
-__device__ __forceinline__ unsigned long long fill_wave_sum(uint32_t x)
-{
-    for (int o = 32; o > 0; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o, 64);
-    return (unsigned long long)x;
-}
 __device__ __forceinline__ float lane_f(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
 __device__ __forceinline__ uint32_t lane_u(uint32_t v, int k) { return (uint32_t)__builtin_amdgcn_readlane((int)v, k); }
 
@@ -325,15 +320,9 @@ __global__ __launch_bounds__(kFillBlock) void atlas_fill_kernel(FillGrid g, cons
         }
     }
     if (stats) {
-        const unsigned long long a = fill_wave_sum(n_decided), b = fill_wave_sum(n_filled);
+        const unsigned long long a = wave_sum_u64(n_decided), b = wave_sum_u64(n_filled);
         if (lane == 0) { atomicAdd(stats, a); atomicAdd(stats + 1, b); }
     }
-}
-
-static int fill_grid_1d(int64_t per_block, int64_t n, int64_t cap)
-{
-    const int64_t want = (n + per_block - 1) / per_block;
-    return (int)(want < 1 ? 1 : (want > cap ? cap : want));
 }
 
 hipError_t launch_atlas_fill(const float* pos, const float* nrm, int64_t Nt, const int32_t* source_ids, int64_t n_src, const int32_t* hole_ids, int64_t n_holes,
@@ -353,16 +342,16 @@ hipError_t launch_atlas_fill(const float* pos, const float* nrm, int64_t Nt, con
     ws += align256(16 * ns);
     float4* recN = (float4*)ws;
     const int n_chunks = (int)((n_cells + kScanChunk - 1) / kScanChunk);
-    hipLaunchKernelGGL(fill_zero_kernel, dim3(fill_grid_1d(kFillBlock, n_cells, 4096)), dim3(kFillBlock), 0, st, cells, n_cells);
+    hipLaunchKernelGGL(fill_zero_kernel, dim3(grid_capped(kFillBlock, n_cells, 4096)), dim3(kFillBlock), 0, st, cells, n_cells);
     if (n_src > 0) {
-        const dim3 bg(fill_grid_1d(kFillBlock, n_src, 8192));
+        const dim3 bg(grid_capped(kFillBlock, n_src, 8192));
         hipLaunchKernelGGL(fill_bin_kernel<false>, bg, dim3(kFillBlock), 0, st, g, pos, nrm, Nt, source_ids, n_src, cells, recP, recN);
         hipLaunchKernelGGL(fill_chunk_sum_kernel, dim3(n_chunks), dim3(kFillBlock), 0, st, cells, n_cells, sums);
         hipLaunchKernelGGL(fill_sums_scan_kernel, dim3(1), dim3(kFillBlock), 0, st, sums, n_chunks);
         hipLaunchKernelGGL(fill_chunk_scan_kernel, dim3(n_chunks), dim3(kFillBlock), 0, st, cells, n_cells, sums);
         hipLaunchKernelGGL(fill_bin_kernel<true>, bg, dim3(kFillBlock), 0, st, g, pos, nrm, Nt, source_ids, n_src, cells, recP, recN);
     }
-    hipLaunchKernelGGL(atlas_fill_kernel, dim3(fill_grid_1d(kFillBlock, n_holes, (int64_t)1 << 20)), dim3(kFillBlock), 0, st, g, pos, nrm, Nt, hole_ids, n_holes, cells,
+    hipLaunchKernelGGL(atlas_fill_kernel, dim3(grid_capped(kFillBlock, n_holes, (int64_t)1 << 20)), dim3(kFillBlock), 0, st, g, pos, nrm, Nt, hole_ids, n_holes, cells,
                        recP, recN, cos_fill, max_dist, src, dist2, stats);
     return hipGetLastError();
 }
