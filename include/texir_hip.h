@@ -106,6 +106,28 @@ TEXIR_API int texir_trace_shade(const texir_scene* scene, const float* org /*dev
                       float t_min, float* radiance /*dev*/, float* t_hit /*dev, nullable*/,
                       uint32_t* prim_id /*dev, nullable*/, float* prim_uv /*dev, nullable*/, void* stream);
 
+/* ---- occlusion query, csrc/occlusion.hip.  Replaces Open3D's RaycastingScene.test_occlusions(rays, tnear, tfar), the sibling of the cast_rays that query_irf
+ * calls (models/tracer_o3d_irt.py:240-269): is anything in the way of the ray inside (t_near, t_far)?
+ *
+ * THE RULE.  occluded[r] = 1 iff SOME triangle passes the leaf test of the closest-hit query for the ray (org[r], dir[r]) with t_near < t < t_far, else 0.
+ * The leaf test is texir_trace_shade's, unchanged: the watertight accept (the vertices moved to the origin and sheared so that dir becomes +z, the three edge
+ * functions with exact signs, zeros inside for both neighbours), det != 0, and t the float32 t that test computes, in units of |dir|.  t_near = 0 gives the
+ * closest-hit query's own t > 0.  Both ends are open: a triangle at exactly t_far does not occlude.
+ *   - At t_near = 0 the answer equals (t_hit < t_far) of texir_trace_shade's t_hit for the same ray, bit for bit, on every ray: the traversal starts with the
+ *     far bound where closest hit starts with +inf and stops at the first accepted triangle; it relies on what the culling of the closest-hit traversal
+ *     already relies on (a box's computed entry distance is never above the computed t of a triangle inside it), so it never skips a box that holds an
+ *     accepted triangle with t < t_far.  tests/test_gpu_occlusion.py binds this equality on every ray of its cases.
+ *   - t_far = NaN or t_far <= t_near: no t qualifies, every ray is "not occluded" and nothing is traced.  t_far = +inf is the whole ray.
+ *   - A zero or non-finite direction is not occluded (closest hit gives a miss there too).
+ * occluded[r] is a pure function of the scene, the ray and the two bounds: no atomics on results; launch shape and stream do not change a byte.
+ *
+ *   org, dir [R,3] dev;  t_near finite and >= 0;  occluded dev [R] u8: one byte per ray, every r < R is written, nothing beyond.
+ *   stats dev u64[1], nullable: += the number of occluded rays; one atomic add per wave.
+ * A negative R, a t_near that is negative or not finite and a null buffer are errors with a texir_last_error() text.  R = 0 returns 0 and writes nothing.
+ * Caller-owned buffers, the caller's stream, no allocation and no synchronisation: the call records into a hipGraph. */
+TEXIR_API int texir_trace_occluded(const texir_scene* scene, const float* org /*dev [R,3]*/, const float* dir /*dev [R,3]*/, int64_t R, float t_near, float t_far,
+                         uint8_t* occluded /*dev [R]*/, uint64_t* stats /*dev [1], nullable*/, void* stream);
+
 /* Replaces generate_dir (utils/sample_util.py:63-146) with pre_mode='Hammersley'.  The per-point random
  * shift (torch.rand(b,1,2) on the CPU generator, :102) is an INPUT so that parity is exact.
  *   normals [b,3] dev, roughness [b] dev (importance only, else NULL), shift [b,2] dev -> L [b,N,3] dev */
@@ -513,6 +535,14 @@ TEXIR_API int texir_atlas_bake(const texir_scene* scene, const float* pos /*dev*
                        int64_t n_ids, int64_t Nt, const float* cams /*dev [K,12]*/, const float* cam_pos /*dev [K,3]*/, const float* panos /*dev [K,h,w,3]*/,
                        const uint8_t* valid /*dev [K,h,w], nullable*/, int32_t K, int32_t h, int32_t w, float cos_min, int32_t* view /*dev [Nt]*/,
                        int32_t* pix /*dev [Nt,2]*/, float* rgb /*dev [Nt,3]*/, uint64_t* stats /*dev [4], nullable*/, void* stream);
+/* texir_atlas_bake with its VISIBILITY step put as the occlusion query texir_trace_occluded(pos, d, 0, 1) instead of a closest-hit query whose t is compared
+ * with 1.  Same parameters, same errors, same house rules.  It returns the bits of texir_atlas_bake: view, pix, rgb and stats alike -- the two queries give
+ * the same answer for every ray (see texir_trace_occluded), and the pairs counted are the same pairs.  What differs is the work: a traversal that stops at
+ * the first accepted triangle and never looks beyond t = 1. */
+TEXIR_API int texir_atlas_bake_any(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const int32_t* texel_ids /*dev, nullable*/,
+                       int64_t n_ids, int64_t Nt, const float* cams /*dev [K,12]*/, const float* cam_pos /*dev [K,3]*/, const float* panos /*dev [K,h,w,3]*/,
+                       const uint8_t* valid /*dev [K,h,w], nullable*/, int32_t K, int32_t h, int32_t w, float cos_min, int32_t* view /*dev [Nt]*/,
+                       int32_t* pix /*dev [Nt,2]*/, float* rgb /*dev [Nt,3]*/, uint64_t* stats /*dev [4], nullable*/, void* stream);
 /* The device form of the four repack*Texture gathers (tools/trans_hdr_tex.py:16-216: radiance, segmentation ids, albedo / roughness predictions of other
  * methods; the pixel is utils/Pano2Cube.py:57-82's): out[t, :] = imgs[view[t], pix[t,0], pix[t,1], :] bit for bit for the listed texels, zeros where
  * view[t] < 0 (or a code points outside the images).  imgs dev [K,h,w,C] f32, C in 1..4; out dev [Nt,C]; texel_ids as above.  Same house rules. */
@@ -625,6 +655,12 @@ TEXIR_API int texir_atlas_fill(const float* pos /*dev*/, const float* nrm /*dev*
  * texir_last_error() text.  K = 0 and an empty list return 0 and write nothing.
  * Caller-owned buffers, the caller's stream, no allocation and no synchronisation: the call records into a hipGraph. */
 TEXIR_API int texir_irt_lights(const texir_scene* scene, const float* pos /*dev [Nt,3]*/, const float* nrm /*dev [Nt,3], raw*/, const float* shift /*dev [Nt,2]*/,
+                       const int32_t* texel_ids /*dev, nullable = all Nt*/, int64_t n_ids, int64_t Nt, const float* lights /*dev [K][16]*/, int32_t K /*0..8*/,
+                       int32_t S /*1..65536*/, float t_max, float* F /*dev [K][Nt]*/, uint64_t* stats /*dev [2], nullable*/, void* stream);
+/* texir_irt_lights with its VISIBILITY step put as the occlusion query texir_trace_occluded(x, d, 0, t_max) instead of a closest-hit query whose t is
+ * compared with t_max.  Same parameters, same errors, same house rules.  It returns the bits of texir_irt_lights: F and stats alike -- the two queries give
+ * the same answer for every ray (see texir_trace_occluded), and the rays counted are the same rays. */
+TEXIR_API int texir_irt_lights_any(const texir_scene* scene, const float* pos /*dev [Nt,3]*/, const float* nrm /*dev [Nt,3], raw*/, const float* shift /*dev [Nt,2]*/,
                        const int32_t* texel_ids /*dev, nullable = all Nt*/, int64_t n_ids, int64_t Nt, const float* lights /*dev [K][16]*/, int32_t K /*0..8*/,
                        int32_t S /*1..65536*/, float t_max, float* F /*dev [K][Nt]*/, uint64_t* stats /*dev [2], nullable*/, void* stream);
 

@@ -50,6 +50,7 @@ def lib():
             "texir_scene_prefetch": [vp, i32, i32, vp],
             "texir_scene_reserve_scratch": [vp, i64, i32],
             "texir_trace_shade": [vp, vp, vp, i64, f32, vp, vp, vp, vp, vp],
+            "texir_trace_occluded": [vp, vp, vp, i64, f32, f32, vp, vp, vp],
             "texir_generate_dir": [vp, vp, vp, i64, i32, i32, vp, vp],
             "texir_irt_generate": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, vp, vp],
             "texir_spec_forward": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp],
@@ -96,6 +97,7 @@ def lib():
         sig["texir_texel_gbuffer_workspace_bytes"] = [vp, i32, i32, C.POINTER(i64)]
         sig["texir_texel_gbuffer"] = [vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp]
         sig["texir_atlas_bake"] = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
+        sig["texir_atlas_bake_any"] = sig["texir_atlas_bake"]
         sig["texir_atlas_gather"] = [vp, vp, vp, i64, i64, vp, i32, i32, i32, i32, vp, vp]
         L.texir_atlas_fill_workspace_bytes.argtypes = [i64, i64]
         L.texir_atlas_fill_workspace_bytes.restype = i64
@@ -103,6 +105,7 @@ def lib():
         L.texir_atlas_fill_cell.restype = f32
         sig["texir_atlas_fill"] = [vp, vp, i64, vp, i64, vp, i64, vp, f32, f32, f32, vp, vp, vp, vp, vp]
         sig["texir_irt_lights"] = [vp, vp, vp, vp, vp, i64, i64, vp, i32, i32, f32, vp, vp, vp]
+        sig["texir_irt_lights_any"] = sig["texir_irt_lights"]
         sig["texir_png_unfilter"] = [vp, i32, i32, i32, vp]
         L.texir_hdr_decode_scanlines.argtypes = [vp, i64, i32, i32, vp]
         L.texir_hdr_decode_scanlines.restype = i64

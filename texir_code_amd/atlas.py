@@ -59,11 +59,14 @@ def _f32(t, dev, shape):
     return torch.as_tensor(t).to(device=dev, dtype=torch.float32).reshape(*shape).contiguous()
 
 
-def bake_atlas(scene, pos, nrm, W, cam_pos, panos, valid=None, cos_min=0.1, texel_ids=None, out=None, stats=False):
+def bake_atlas(scene, pos, nrm, W, cam_pos, panos, valid=None, cos_min=0.1, texel_ids=None, out=None, stats=False, query="closest"):
     """texir_atlas_bake.  pos (already offset), nrm [..,3]; W [K,3,4], cam_pos [K,3] (camera_matrices); panos [K,h,w,3] float32; valid [K,h,w] uint8 or None;
     texel_ids: int32 list of the texels to decide (None: all; pass dist_util.morton_order's order) -> view [Nt] int32 (-1: no view), pix [Nt,2] int32
     (row, col), rgb [Nt,3] float32.  Unlisted texels keep what `out` = (view, pix, rgb) held (fresh buffers: view -1, zeros).  stats=True adds a
-    [4] int64 tensor (pairs facing, pairs traced, pairs visible, texels assigned).  Launches on the current stream, no synchronisation."""
+    [4] int64 tensor (pairs facing, pairs traced, pairs visible, texels assigned).  query: 'closest' | 'any' (texir_atlas_bake_any: the segment test as an
+    occlusion query, the same bits).  Launches on the current stream, no synchronisation."""
+    from .scene import check_query
+    call = "texir_atlas_bake_any" if check_query(query, "bake_atlas: query") else "texir_atlas_bake"
     dev = scene.device
     pos, nrm = _f32(pos, dev, (-1, 3)), _f32(nrm, dev, (-1, 3))
     Nt = pos.shape[0]
@@ -88,8 +91,8 @@ def bake_atlas(scene, pos, nrm, W, cam_pos, panos, valid=None, cos_min=0.1, texe
         n_ids = ids.numel()
     st = torch.zeros(4, device=dev, dtype=torch.int64) if stats else None
     if Nt > 0 and not (texel_ids is not None and n_ids == 0):          # (an empty list must not reach the library: NULL means all texels)
-        _lib.check(_lib.lib().texir_atlas_bake(scene.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(ids), n_ids, Nt, _lib.ptr(W), _lib.ptr(cam_pos), _lib.ptr(panos),
-                                               _lib.ptr(valid), K, h, w, float(cos_min), _lib.ptr(view), _lib.ptr(pix), _lib.ptr(rgb), _lib.ptr(st), _lib.stream_ptr()))
+        _lib.check(getattr(_lib.lib(), call)(scene.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(ids), n_ids, Nt, _lib.ptr(W), _lib.ptr(cam_pos), _lib.ptr(panos),
+                                             _lib.ptr(valid), K, h, w, float(cos_min), _lib.ptr(view), _lib.ptr(pix), _lib.ptr(rgb), _lib.ptr(st), _lib.stream_ptr()))
     return (view, pix, rgb, st) if stats else (view, pix, rgb)
 
 
@@ -276,7 +279,7 @@ def _packs_exactly(rgb):
     return bool(ok.all())
 
 
-def bake_files(root, H, W_atlas, out_dir=None, cos_min=0.1, normal="geometric", seg=False, device=0, fill=False, fill_dist=0.5, fill_cos=0.5):
+def bake_files(root, H, W_atlas, out_dir=None, cos_min=0.1, normal="geometric", seg=False, device=0, fill=False, fill_dist=0.5, fill_cos=0.5, query="closest"):
     """the command: mesh + extrinsics + hdr/<id>/ccm.hdr (+ the alpha of derived/<id>/panoImage_orig.jpg as the mask) -> hdr_texture.hdr, 0.png
     (+ 0_seg_gray.png) in out_dir.  Returns a dict (paths, the share of covered texels that got a view, the device arrays).
     fill=True completes the atlas before it is written: unobserved covered texels from the nearest compatible observed texel in world space (fill_atlas,
@@ -320,7 +323,7 @@ def bake_files(root, H, W_atlas, out_dir=None, cos_min=0.1, normal="geometric", 
     covered = torch.nonzero(prim.reshape(-1) >= 0)[:, 0].to(torch.int32)
     order = dist_util.morton_order(covered, W_atlas)
     Wm, cam = camera_matrices(E)
-    view, pix, rgb = bake_atlas(scene, pos, nrm, Wm, cam, np.stack(panos, 0), valid, cos_min, texel_ids=order)
+    view, pix, rgb = bake_atlas(scene, pos, nrm, Wm, cam, np.stack(panos, 0), valid, cos_min, texel_ids=order, query=query)
     os.makedirs(out_dir, exist_ok=True)
     res = {"dir": out_dir, "view": view, "pix": pix, "rgb": rgb, "covered": int(covered.numel()), "hw": (h, w), "view_count": len(ids)}
     fill_src = filled_ids = None

@@ -328,6 +328,18 @@ int texir_trace_shade(const texir_scene* s, const float* org, const float* dir, 
     return TEXIR_OK;
 }
 
+/* the any-hit query, csrc/occlusion.hip: Open3D RaycastingScene.test_occlusions, the sibling of the cast_rays at models/tracer_o3d_irt.py:240-269 */
+int texir_trace_occluded(const texir_scene* s, const float* org, const float* dir, int64_t R, float t_near, float t_far, uint8_t* occluded, uint64_t* stats,
+                         void* stream)
+{
+    if (R < 0) return fail(TEXIR_ERR_INVALID, "texir_trace_occluded: negative ray count");
+    if (!(t_near >= 0.0f) || !(t_near - t_near == 0.0f)) return fail(TEXIR_ERR_INVALID, "texir_trace_occluded: t_near must be finite and >= 0");
+    if (R == 0) return TEXIR_OK;
+    if (!s || !org || !dir || !occluded) return fail(TEXIR_ERR_INVALID, "texir_trace_occluded: null argument (scene, org, dir and occluded are required)");
+    HIP_TRY(launch_trace_occluded(dev_of(s), org, dir, R, t_near, t_far, occluded, (unsigned long long*)stats, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 int texir_generate_dir(const float* normals, const float* roughness, const float* shift, int64_t b, int32_t N, int32_t mode, float* L, void* stream)
 {
     if (!normals || !shift || !L) return fail(TEXIR_ERR_INVALID, "texir_generate_dir: null argument");
@@ -697,19 +709,34 @@ int texir_texel_gbuffer(const texir_scene* s, int32_t H, int32_t W, int32_t norm
 /* ---- the radiance atlas + index texture from calibrated panoramas, csrc/texbake.hip.  The reference has no producer of either file: its private capture
  * pipeline writes 0.png and tools/trans_hdr_tex.py:16-61 (repackHDRTexture) only gathers the panoramas' pixels through those codes; the panorama pixel of
  * a direction is the one utils/Pano2Cube.py:57-82 reads (grid_sample nearest, align_corners=False). ---- */
+static int atlas_bake_call(const char* fn, bool any, const texir_scene* s, const float* pos, const float* nrm, const int32_t* texel_ids, int64_t n_ids, int64_t Nt,
+                           const float* cams, const float* cam_pos, const float* panos, const uint8_t* valid, int32_t K, int32_t h, int32_t w, float cos_min,
+                           int32_t* view, int32_t* pix, float* rgb, uint64_t* stats, void* stream)
+{
+    if (!s || !pos || !nrm || !cams || !cam_pos || !panos) return fail(TEXIR_ERR_INVALID, "%s: null argument (scene, pos, nrm, cams, cam_pos and panos are required)", fn);
+    if (!view || !pix || !rgb) return fail(TEXIR_ERR_INVALID, "%s: null output (view, pix and rgb are required)", fn);
+    if (K < 1) return fail(TEXIR_ERR_INVALID, "%s: K must be >= 1 (got %d)", fn, K);
+    if (h < 1 || w < 1 || h > 32768 || w > 32768) return fail(TEXIR_ERR_INVALID, "%s: h and w must be 1..32768 (got %d x %d)", fn, h, w);
+    if (Nt < 0 || (texel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "%s: negative texel count", fn);
+    if (!(cos_min - cos_min == 0.0f)) return fail(TEXIR_ERR_INVALID, "%s: cos_min must be finite", fn);
+    HIP_TRY(launch_atlas_bake(dev_of(s), pos, nrm, texel_ids, texel_ids ? n_ids : Nt, Nt, cams, cam_pos, panos, valid, K, h, w, cos_min, view, pix, rgb,
+                              (unsigned long long*)stats, (hipStream_t)stream, any));
+    return TEXIR_OK;
+}
+
 int texir_atlas_bake(const texir_scene* s, const float* pos, const float* nrm, const int32_t* texel_ids, int64_t n_ids, int64_t Nt, const float* cams,
                      const float* cam_pos, const float* panos, const uint8_t* valid, int32_t K, int32_t h, int32_t w, float cos_min, int32_t* view, int32_t* pix,
                      float* rgb, uint64_t* stats, void* stream)
 {
-    if (!s || !pos || !nrm || !cams || !cam_pos || !panos) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: null argument (scene, pos, nrm, cams, cam_pos and panos are required)");
-    if (!view || !pix || !rgb) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: null output (view, pix and rgb are required)");
-    if (K < 1) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: K must be >= 1 (got %d)", K);
-    if (h < 1 || w < 1 || h > 32768 || w > 32768) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: h and w must be 1..32768 (got %d x %d)", h, w);
-    if (Nt < 0 || (texel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: negative texel count");
-    if (!(cos_min - cos_min == 0.0f)) return fail(TEXIR_ERR_INVALID, "texir_atlas_bake: cos_min must be finite");
-    HIP_TRY(launch_atlas_bake(dev_of(s), pos, nrm, texel_ids, texel_ids ? n_ids : Nt, Nt, cams, cam_pos, panos, valid, K, h, w, cos_min, view, pix, rgb,
-                              (unsigned long long*)stats, (hipStream_t)stream));
-    return TEXIR_OK;
+    return atlas_bake_call("texir_atlas_bake", false, s, pos, nrm, texel_ids, n_ids, Nt, cams, cam_pos, panos, valid, K, h, w, cos_min, view, pix, rgb, stats, stream);
+}
+
+/* the same bake with the segment test as an any-hit query (trace_occluded): the bits of texir_atlas_bake */
+int texir_atlas_bake_any(const texir_scene* s, const float* pos, const float* nrm, const int32_t* texel_ids, int64_t n_ids, int64_t Nt, const float* cams,
+                         const float* cam_pos, const float* panos, const uint8_t* valid, int32_t K, int32_t h, int32_t w, float cos_min, int32_t* view, int32_t* pix,
+                         float* rgb, uint64_t* stats, void* stream)
+{
+    return atlas_bake_call("texir_atlas_bake_any", true, s, pos, nrm, texel_ids, n_ids, Nt, cams, cam_pos, panos, valid, K, h, w, cos_min, view, pix, rgb, stats, stream);
 }
 
 /* the gathers of tools/trans_hdr_tex.py:16-216 (repackHDRTexture, repackSegTexture, repackAlbedoTexture, repackRoughnessTexture: pixel (row, col) of
@@ -767,20 +794,33 @@ int texir_atlas_fill(const float* pos, const float* nrm, int64_t Nt, const int32
 
 /* ---- inserted emitters, csrc/irtlight.hip: the direct irradiance factor F of K new area lights per listed texel (the "moving" half of
  * tools/relighting_varying.py leaves the reference for an external renderer; include/texir_hip.h states the rule) ---- */
+static int irt_lights_call(const char* fn, bool any, const texir_scene* s, const float* pos, const float* nrm, const float* shift, const int32_t* texel_ids,
+                           int64_t n_ids, int64_t Nt, const float* lights, int32_t K, int32_t S, float t_max, float* F, uint64_t* stats, void* stream)
+{
+    // (K first: a caller that sized `lights` and `F` by a bad K may hold no buffer at all)
+    if (K < 0 || K > 8) return fail(TEXIR_ERR_INVALID, "%s: K must be in 0..8, got %d (call again for further lights: the factors add)", fn, K);
+    if (S < 1 || S > 65536) return fail(TEXIR_ERR_INVALID, "%s: S must be in 1..65536, got %d", fn, S);
+    if (!(t_max - t_max == 0.0f)) return fail(TEXIR_ERR_INVALID, "%s: t_max must be finite", fn);
+    if (Nt < 0 || (texel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "%s: negative texel count", fn);
+    if (Nt >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "%s: Nt too large", fn);
+    const int64_t n = texel_ids ? n_ids : Nt;
+    if (K == 0 || n == 0) return TEXIR_OK;
+    if (!s || !pos || !nrm || !shift || !lights || !F) return fail(TEXIR_ERR_INVALID, "%s: null argument (scene, pos, nrm, shift, lights and F are required)", fn);
+    HIP_TRY(launch_irt_lights(dev_of(s), pos, nrm, shift, texel_ids, n, Nt, lights, K, S, t_max, F, (unsigned long long*)stats, (hipStream_t)stream, any));
+    return TEXIR_OK;
+}
+
 int texir_irt_lights(const texir_scene* s, const float* pos, const float* nrm, const float* shift, const int32_t* texel_ids, int64_t n_ids, int64_t Nt,
                      const float* lights, int32_t K, int32_t S, float t_max, float* F, uint64_t* stats, void* stream)
 {
-    // (K first: a caller that sized `lights` and `F` by a bad K may hold no buffer at all)
-    if (K < 0 || K > 8) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: K must be in 0..8, got %d (call again for further lights: the factors add)", K);
-    if (S < 1 || S > 65536) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: S must be in 1..65536, got %d", S);
-    if (!(t_max - t_max == 0.0f)) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: t_max must be finite");
-    if (Nt < 0 || (texel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: negative texel count");
-    if (Nt >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: Nt too large");
-    const int64_t n = texel_ids ? n_ids : Nt;
-    if (K == 0 || n == 0) return TEXIR_OK;
-    if (!s || !pos || !nrm || !shift || !lights || !F) return fail(TEXIR_ERR_INVALID, "texir_irt_lights: null argument (scene, pos, nrm, shift, lights and F are required)");
-    HIP_TRY(launch_irt_lights(dev_of(s), pos, nrm, shift, texel_ids, n, Nt, lights, K, S, t_max, F, (unsigned long long*)stats, (hipStream_t)stream));
-    return TEXIR_OK;
+    return irt_lights_call("texir_irt_lights", false, s, pos, nrm, shift, texel_ids, n_ids, Nt, lights, K, S, t_max, F, stats, stream);
+}
+
+/* the same factors with visibility as an any-hit query (trace_occluded): the bits of texir_irt_lights */
+int texir_irt_lights_any(const texir_scene* s, const float* pos, const float* nrm, const float* shift, const int32_t* texel_ids, int64_t n_ids, int64_t Nt,
+                         const float* lights, int32_t K, int32_t S, float t_max, float* F, uint64_t* stats, void* stream)
+{
+    return irt_lights_call("texir_irt_lights_any", true, s, pos, nrm, shift, texel_ids, n_ids, Nt, lights, K, S, t_max, F, stats, stream);
 }
 
 }  // extern "C"

@@ -362,13 +362,18 @@ constexpr int kWiCulled = 2 + kProbeSlots, kWiOverflow = 3 + kProbeSlots, kWiSlo
 template <bool CULL> struct StackEntry { typedef int type; };
 template <> struct StackEntry<true> { typedef int2 type; };
 
-// trace_core is the traversal; trace_closest (one ray per lane, run to completion) and trace_stream (lanes take their NEXT ray while the others
-// are still under way: compaction by refill, see there) are its two drivers.
+// trace_core is the traversal; trace_closest (one ray per lane, run to completion), trace_stream (lanes take their NEXT ray while the others
+// are still under way: compaction by refill, see there) and trace_occluded (any hit inside a segment, see there) are its three drivers.
+// ANY: the any-hit form.  h.t starts at the segment's far end `t_start` instead of +inf -- the box tests, the culling pops and the leaf's t < h.t then
+// apply the far bound as they apply a closest hit -- a triangle is accepted beyond `t_near` instead of beyond 0, and a lane that has accepted one empties
+// its stack at the end of that leaf: the pop that ends the leaf finds nothing and the lane is finished, nothing is drained.  The accept test is the one
+// expression of the closest-hit form: a triangle's t and its inside test do not depend on h.t.
 struct NoNext { };
-template <bool STATS, int LSTK, int WIDTH, bool CULL, bool STREAM, typename Next>
+template <bool STATS, int LSTK, int WIDTH, bool CULL, bool STREAM, bool ANY, typename Next>
 __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy, float oz, float dx, float dy, float dz,
-                                          uint32_t& n_nodes, uint32_t& n_tris, uint32_t* wave_iters, int refill_at, Next&& next)
+                                          uint32_t& n_nodes, uint32_t& n_tris, uint32_t* wave_iters, int refill_at, Next&& next, float t_start, float t_near)
 {
+    static_assert(!(ANY && STREAM), "the any-hit form runs one ray per lane to completion");
     typedef typename StackEntry<CULL>::type Entry;
     // what the traversal keeps of a ray (set by begin_ray; a streamed lane overwrites them when it takes its next ray)
     float idx, idy, idz, oodx, oody, oodz;
@@ -432,7 +437,8 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
     };
     agree(true);
     Hit h;
-    h.t = __builtin_inff(); h.u = 0.f; h.v = 0.f; h.slot = -1;
+    h.t = t_start; h.u = 0.f; h.v = 0.f; h.slot = -1;
+    const float t_accept = ANY ? t_near : 0.f;                 // a triangle is accepted beyond it
     int node = STREAM ? kSentinel : 0;                       // (a streamed lane gets its first ray from `next` like every later one)
     auto first_active = [&]() -> bool { unsigned long long m = __ballot(1); return (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1; };
     // the traversal stack: LSTK entries per lane in LDS ([entry][thread]), deeper ones private.  The stack pointer is kept as
@@ -684,7 +690,7 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
                     const float inv = __builtin_amdgcn_rcpf(det);
                     const float t = (U * Az + V * Bz + W * Cz) * inv;
                     const float u = V * inv, v = W * inv;
-                    const bool ok = !((mn < 0.f) & (mxw > 0.f)) & (det != 0.f) & (t > 0.f) & (t < h.t);
+                    const bool ok = !((mn < 0.f) & (mxw > 0.f)) & (det != 0.f) & (t > t_accept) & (t < h.t);
                     if (ok) { h.t = t; h.u = u; h.v = v; h.slot = slot; }
                 };
                 // triangle 0 = (A, B, C) = (q0, q1, q2): U = e(B, C), V = e(C, A), W = e(A, B)
@@ -692,6 +698,7 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
                 // triangle 1 = (A, B, C) = (q3, q2, q1): U = e(q2, q1) = -e(q1, q2), V = e(q1, q3), W = e(q3, q2)
                 accept(-E12, edge2_exact(X1, Y1, X3, Y3), edge2_exact(X3, Y3, X2, Y2), Z3, Z2, Z1, 2 * r + 1);
             }
+            if constexpr (ANY) { if (h.slot >= 0) top = base; }          // occluded: the lane's stack is dropped whole, the pop below returns the sentinel
             node = leaf_pop();
             return;
         }
@@ -722,7 +729,7 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             const float t = (U * Az + V * Bz + W * Cz) * inv;
             const float u = V * inv, v = W * inv;
             // inside <=> no two of the signs differ (zeros -- the origin exactly on an edge or vertex -- count as inside for BOTH neighbours)
-            const bool ok = !((mn < 0.f) & (mxw > 0.f)) & (det != 0.f) & (t > 0.f) & (t < h.t);
+            const bool ok = !((mn < 0.f) & (mxw > 0.f)) & (det != 0.f) & (t > t_accept) & (t < h.t);
 #else
             // Moeller-Trumbore, same operation order as the oracle
             float px = dy * e2.z - dz * e2.y, py = dz * e2.x - dx * e2.z, pz = dx * e2.y - dy * e2.x;
@@ -733,10 +740,11 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             float qx = ty * e1.z - tz * e1.y, qy = tz * e1.x - tx * e1.z, qz = tx * e1.y - ty * e1.x;
             float v = (dx * qx + dy * qy + dz * qz) * inv;
             float t = (e2.x * qx + e2.y * qy + e2.z * qz) * inv;
-            bool ok = (det != 0.f) & (u >= 0.f) & (u <= 1.f) & (v >= 0.f) & (u + v <= 1.f) & (t > 0.f) & (t < h.t);
+            bool ok = (det != 0.f) & (u >= 0.f) & (u <= 1.f) & (v >= 0.f) & (u + v <= 1.f) & (t > t_accept) & (t < h.t);
 #endif
             if (ok) { h.t = t; h.u = u; h.v = v; h.slot = i; }
         }
+        if constexpr (ANY) { if (h.slot >= 0) top = base; }
         node = leaf_pop();
     };
     auto leaf_step = [&]() __attribute__((always_inline)) {
@@ -834,7 +842,7 @@ template <bool STATS, int LSTK = kLdsStack, int WIDTH = 2, bool CULL = false>
 __device__ __forceinline__ Hit trace_closest(const SceneDev& sc, float ox, float oy, float oz, float dx, float dy, float dz,
                                              uint32_t& n_nodes, uint32_t& n_tris, uint32_t* wave_iters = nullptr)
 {
-    return trace_core<STATS, LSTK, WIDTH, CULL, false>(sc, ox, oy, oz, dx, dy, dz, n_nodes, n_tris, wave_iters, 64, NoNext{});
+    return trace_core<STATS, LSTK, WIDTH, CULL, false, false>(sc, ox, oy, oz, dx, dy, dz, n_nodes, n_tris, wave_iters, 64, NoNext{}, __builtin_inff(), 0.f);
 }
 
 // Streamed form: every ray of the lane, the first one included, comes from `next`, which is called for the idle lanes once `refill_at` of them have
@@ -844,7 +852,21 @@ template <bool STATS, int LSTK, int WIDTH, bool CULL, typename Next>
 __device__ __forceinline__ void trace_stream(const SceneDev& sc, float ox, float oy, float oz, uint32_t& n_nodes, uint32_t& n_tris, uint32_t* wave_iters,
                                              int refill_at, Next&& next)
 {
-    (void)trace_core<STATS, LSTK, WIDTH, CULL, true>(sc, ox, oy, oz, 0.f, 0.f, 0.f, n_nodes, n_tris, wave_iters, refill_at, next);
+    (void)trace_core<STATS, LSTK, WIDTH, CULL, true, false>(sc, ox, oy, oz, 0.f, 0.f, 0.f, n_nodes, n_tris, wave_iters, refill_at, next, __builtin_inff(), 0.f);
+}
+
+// Any hit inside a segment, one ray per lane, run to completion: true iff some triangle passes the leaf test above with t_near < t < t_far, t the float32 t
+// that test computes (include/texir_hip.h, texir_trace_occluded, states the rule).  At t_near = 0 this is the answer of `trace_closest(...).t < t_far`, bit for
+// bit: a box's computed entry distance is never above the computed t of a triangle inside it (what CULL already relies on), so a walk that starts with
+// h.t = t_far never culls a box that holds an accepted triangle with t < t_far, and "the closest accepted t is below t_far" says the same as "an accepted
+// triangle with t < t_far exists".  A lane stops at the end of the first leaf that accepts a triangle; a segment without one walks the boxes it crosses up
+// to t_far, in no particular need of their order.  t_far = NaN or <= t_near accepts nothing; a zero or non-finite direction accepts nothing (as closest hit).
+// One instance per kernel, like trace_closest: it owns the LDS part of the stacks.
+template <int LSTK, int WIDTH, bool CULL>
+__device__ __forceinline__ bool trace_occluded(const SceneDev& sc, float ox, float oy, float oz, float dx, float dy, float dz, float t_near, float t_far)
+{
+    uint32_t cn = 0, ct = 0;
+    return trace_core<false, LSTK, WIDTH, CULL, false, true>(sc, ox, oy, oz, dx, dy, dz, cn, ct, nullptr, 64, NoNext{}, t_far, t_near).slot >= 0;
 }
 
 __device__ __forceinline__ float wave_sum(float x)

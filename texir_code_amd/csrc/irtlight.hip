@@ -8,6 +8,8 @@
 // w + waves, ... -- no work counter, no wave waits on another, every loop is bounded by K, S, the item count or the traversal's own bounds.  The light record
 // is a wave-uniform (scalar) load; the sample loop runs over i for the whole wave; a sample no lane of the wave needs is skipped by ballot.  Visibility is ONE
 // closest-hit query (device_common.h trace_closest<false, kLstk, WIDTH, kCull>, the single-ray kernels' shared form): occluded iff the closest hit has t < t_max.
+// ANY (texir_irt_lights_any): the same question put to trace_occluded<kLstk, WIDTH, kCull>(..., 0, t_max), which stops at the first accepted triangle: the
+// same answer per ray (see there), hence the same F and the same counts, bit for bit.
 // F is a pure function of the inputs: one float32 accumulator per (texel, light) in ascending i, no atomics on results, no workspace.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,7 +23,7 @@ namespace texir {
 
 constexpr float kTwoPi32 = 6.28318548202514648f, kFourPi32 = 12.5663709640502930f;      // the float32 neighbours of 2 pi and 4 pi
 
-template <int WIDTH>
+template <int WIDTH, bool ANY>
 __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm, const float* __restrict__ shift,
                                                             const int32_t* __restrict__ ids, int64_t n, int64_t Nt, const float* __restrict__ lights, int K, int S,
                                                             float t_max, float* __restrict__ F, unsigned long long* __restrict__ stats)
@@ -94,10 +96,17 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
                 if (!__any(need)) continue;                                 // no lane of the wave needs this sample
                 if (need) {
                     it_traced++;
-                    const Hit hit = trace_closest<false, kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
-                    if (!(hit.slot >= 0 && hit.t < t_max)) {
-                        it_visible++;
-                        acc += g;
+                    if constexpr (ANY) {
+                        if (!trace_occluded<kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, 0.f, t_max)) {
+                            it_visible++;
+                            acc += g;
+                        }
+                    } else {
+                        const Hit hit = trace_closest<false, kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
+                        if (!(hit.slot >= 0 && hit.t < t_max)) {
+                            it_visible++;
+                            acc += g;
+                        }
                     }
                 }
             }
@@ -114,15 +123,14 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
 #pragma clang fp contract(fast)
 
 hipError_t launch_irt_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids, int64_t n, int64_t Nt,
-                             const float* lights, int K, int S, float t_max, float* F, unsigned long long* stats, hipStream_t st)
+                             const float* lights, int K, int S, float t_max, float* F, unsigned long long* stats, hipStream_t st, bool any)
 {
     if (n <= 0 || K <= 0) return hipSuccess;
     const int64_t items = ((n + 63) / 64) * K;
     const int grid = grid_capped(kBlock / 64, items);      // a fixed cap: nothing is queried per launch (the result does not depend on the grid)
-    if (sc.nodes4)
-        hipLaunchKernelGGL(irt_lights_kernel<4>, dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n, Nt, lights, K, S, t_max, F, stats);
-    else
-        hipLaunchKernelGGL(irt_lights_kernel<2>, dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n, Nt, lights, K, S, t_max, F, stats);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n, Nt, lights, K, S, t_max, F, stats); };
+    if (sc.nodes4) { if (any) go(irt_lights_kernel<4, true>); else go(irt_lights_kernel<4, false>); }
+    else { if (any) go(irt_lights_kernel<2, true>); else go(irt_lights_kernel<2, false>); }
     return hipGetLastError();
 }
 

@@ -69,7 +69,7 @@ hipError_t launch_texel_raster(const SceneDev& sc, const float4* cnrm /*nullable
 // texbake.hip: the radiance atlas and the index texture from calibrated panoramas (tools/trans_hdr_tex.py:16-61 gathers through the codes this selects)
 hipError_t launch_atlas_bake(const SceneDev& sc, const float* pos, const float* nrm, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt, const float* cams,
                              const float* cam_pos, const float* panos, const uint8_t* valid /*nullable*/, int K, int h, int w, float cos_min, int32_t* view, int32_t* pix,
-                             float* rgb, unsigned long long* stats /*nullable*/, hipStream_t st);
+                             float* rgb, unsigned long long* stats /*nullable*/, hipStream_t st, bool any = false /*the segment test as an any-hit query: same bits*/);
 hipError_t launch_atlas_gather(const int32_t* view, const int32_t* pix, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt, const float* imgs, int K, int h,
                                int w, int C, float* out, hipStream_t st);
 // texfill.hip: unobserved texels of a baked atlas from the nearest observed texel in world space whose normal agrees (exact grid search)
@@ -84,7 +84,11 @@ size_t irt_split_workspace_bytes(int64_t n_ids, int N, int K);       // 0 for ar
 hipError_t launch_irt_split(const SceneDev& sc, const float* tex_row_major, const uint8_t* labels, const float* pos, const float* nrm, const float* shift,
                             const int32_t* ids /*nullable: all Nt*/, int64_t n_ids, int64_t Nt, int N, int mode, int K, int unit, float* out /*[K][Nt][3]*/,
                             float* partial /*>= irt_split_workspace_bytes()*/, hipStream_t st);
-// irtlight.hip: direct irradiance factors of inserted area lights (quads, spheres) per listed texel, one closest-hit query per sample
+// irtlight.hip: direct irradiance factors of inserted area lights (quads, spheres) per listed texel, one closest-hit (any = true: any-hit, same bits) query per sample
 hipError_t launch_irt_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt,
-                             const float* lights /*dev [K][16]*/, int K, int S, float t_max, float* F /*[K][Nt]*/, unsigned long long* stats /*nullable*/, hipStream_t st);
+                             const float* lights /*dev [K][16]*/, int K, int S, float t_max, float* F /*[K][Nt]*/, unsigned long long* stats /*nullable*/, hipStream_t st,
+                             bool any = false);
+// occlusion.hip: is anything in the way inside (t_near, t_far)?  One any-hit query per ray (Open3D RaycastingScene.test_occlusions)
+hipError_t launch_trace_occluded(const SceneDev& sc, const float* org, const float* dir, int64_t R, float t_near, float t_far, uint8_t* occluded,
+                                 unsigned long long* stats /*nullable*/, hipStream_t st);
 }  // namespace texir

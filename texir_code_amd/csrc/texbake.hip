@@ -9,6 +9,8 @@
 // A lane traces a view only when it faces it, its pixel is valid and its score beats the lane's best so far (views come in ascending order, so a tie never
 // replaces an earlier view: the lowest id keeps it); a view no lane of the wave needs is skipped by ballot.  The segment test is ONE closest-hit query
 // (device_common.h trace_closest<false, kLstk, WIDTH, kCull>, the single-ray kernels' shared form) with org = pos, dir = camera - pos: the view is occluded iff the closest hit has t < 1.
+// ANY (texir_atlas_bake_any): the same question put to trace_occluded<kLstk, WIDTH, kCull>(..., 0, 1), which stops at the first accepted triangle: the same
+// answer per pair (see there), hence the same view, pix, rgb and counts, bit for bit.
 // The outcome per texel is a pure function of the inputs: no atomics on results, nothing depends on the list's order or the launch shape.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,7 +43,7 @@ __device__ __forceinline__ bool pano_pixel(const float* __restrict__ Wm, float p
     return true;
 }
 
-template <int WIDTH>
+template <int WIDTH, bool ANY>
 __global__ __launch_bounds__(kBlock) void atlas_bake_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm, const int32_t* __restrict__ ids,
                                                             int64_t n, int64_t Nt, const float* __restrict__ cams, const float* __restrict__ cam_pos,
                                                             const uint32_t* __restrict__ panos, const uint8_t* __restrict__ valid, int K, int h, int w, float cos_min,
@@ -82,8 +84,13 @@ __global__ __launch_bounds__(kBlock) void atlas_bake_kernel(SceneDev sc, const f
             if (!__any(need)) continue;                                    // no lane of the wave needs this view
             if (need) {
                 n_traced++;
-                const Hit hit = trace_closest<false, kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
-                if (!(hit.slot >= 0 && hit.t < 1.f)) {
+                bool occluded;
+                if constexpr (ANY) occluded = trace_occluded<kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, 0.f, 1.f);
+                else {
+                    const Hit hit = trace_closest<false, kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
+                    occluded = hit.slot >= 0 && hit.t < 1.f;
+                }
+                if (!occluded) {
                     n_visible++;
                     best_k = k; best_s = s; best_row = row; best_col = col;
                 }
@@ -125,16 +132,16 @@ __global__ __launch_bounds__(256) void atlas_gather_kernel(const int32_t* __rest
 
 hipError_t launch_atlas_bake(const SceneDev& sc, const float* pos, const float* nrm, const int32_t* ids, int64_t n, int64_t Nt, const float* cams, const float* cam_pos,
                              const float* panos, const uint8_t* valid, int K, int h, int w, float cos_min, int32_t* view, int32_t* pix, float* rgb,
-                             unsigned long long* stats, hipStream_t st)
+                             unsigned long long* stats, hipStream_t st, bool any)
 {
     if (n <= 0) return hipSuccess;
     const dim3 grid(grid_capped(kBlock, n));
-    if (sc.nodes4)
-        hipLaunchKernelGGL(atlas_bake_kernel<4>, grid, dim3(kBlock), 0, st, sc, pos, nrm, ids, n, Nt, cams, cam_pos, (const uint32_t*)panos, valid, K, h, w, cos_min,
-                           view, pix, (uint32_t*)rgb, stats);
-    else
-        hipLaunchKernelGGL(atlas_bake_kernel<2>, grid, dim3(kBlock), 0, st, sc, pos, nrm, ids, n, Nt, cams, cam_pos, (const uint32_t*)panos, valid, K, h, w, cos_min,
-                           view, pix, (uint32_t*)rgb, stats);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, sc, pos, nrm, ids, n, Nt, cams, cam_pos, (const uint32_t*)panos, valid, K, h, w, cos_min, view, pix,
+                           (uint32_t*)rgb, stats);
+    };
+    if (sc.nodes4) { if (any) go(atlas_bake_kernel<4, true>); else go(atlas_bake_kernel<4, false>); }
+    else { if (any) go(atlas_bake_kernel<2, true>); else go(atlas_bake_kernel<2, false>); }
     return hipGetLastError();
 }
 

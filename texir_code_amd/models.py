@@ -66,6 +66,14 @@ def _load_scene(conf, device):
     return scene, obj, torch.from_numpy(tex)
 
 
+def irt_light_query(value):
+    """train.irt_light_query: closest | any (Scene.irt_lights' query) -> the value in lower case; anything else raises ValueError"""
+    from .scene import check_query
+    v = str(value).strip().lower()
+    check_query(v, "train.irt_light_query")
+    return v
+
+
 def seam_texels(index_texture):
     """texels the reference zeroes: `index_texture[:,:,0] + index_texture[:,:,1] + index_texture[:,:,2] == 0` evaluated in the image's own
     uint16 arithmetic (tracer_o3d_irt.py:137,176): a code triple whose sum wraps to 65536 counts as a seam there, and so it does here"""
@@ -146,6 +154,8 @@ class TracerO3d(nn.Module):
         # every listed light at train.irt_light_samples (64) samples per texel (Scene.irt_lights)
         self.irt_lights = str(conf.get("train.irt_lights", "none"))
         self.irt_light_samples = conf.get_int("train.irt_light_samples", 64)
+        # train.irt_light_query (optional key): closest (default) | any: the light pass's visibility as an occlusion query (Scene.irt_lights(query=...): same files)
+        self.irt_light_query = irt_light_query(conf.get("train.irt_light_query", "closest"))
         self.ir_lights = None
         # optional exact texel G-buffer written by the synthetic generator (bypasses the panorama gather)
         self.texel_gbuffer_path = _sibling(self.path_traced_mesh, "texel_gbuffer.npz")
@@ -275,7 +285,8 @@ class TracerO3d(nn.Module):
             with phases.phase("irt_lights"):
                 from . import irtlight
                 records, _ = irtlight.load(self.irt_lights)
-                self.ir_lights = self.scene.irt_lights(pos, nrm, shift, torch.from_numpy(records), self.irt_light_samples, texel_ids=ids).reshape(-1, H, W)
+                self.ir_lights = self.scene.irt_lights(pos, nrm, shift, torch.from_numpy(records), self.irt_light_samples, texel_ids=ids,
+                                                        query=self.irt_light_query).reshape(-1, H, W)
         self.ir_texture = irr.reshape(H, W, 3)
         return self.ir_texture
 

@@ -8,6 +8,15 @@ import torch
 from . import _lib
 
 MODES = {"uniform": 0, "cosine": 1, "importance": 2}
+QUERIES = ("closest", "any")
+
+
+def check_query(query, what="query"):
+    """the visibility query of the bake and the light pass: 'closest' (one closest-hit query per ray, its t compared with the far bound) | 'any' (one
+    occlusion query per ray, texir_trace_occluded's traversal: the same bits) -> True for 'any'; anything else raises ValueError"""
+    if query not in QUERIES:
+        raise ValueError("%s must be 'closest' or 'any', got %r" % (what, query))
+    return query == "any"
 
 # hipFree is not allowed while a stream capture (hipGraph) is in progress, and a Scene may be garbage-collected at any time:
 # destruction is deferred while this counter is non-zero (see defer_destroy()).
@@ -125,6 +134,27 @@ class Scene:
                                                     _lib.ptr(pid), _lib.ptr(uv), _lib.stream_ptr()))
         return (rad, t, pid, uv) if return_hits else rad
 
+    # -- RaycastingScene.test_occlusions, the sibling of the cast_rays above (include/texir_hip.h texir_trace_occluded) ------------
+    def test_occlusions(self, org, dir, t_near=0.0, t_far=float("inf"), out=None, stats=False):
+        """is anything in the way of the ray inside (t_near, t_far), t in units of |dir|?  org, dir [..., 3] (any leading shape, as trace_shade takes) ->
+        bool [R], R the number of rays: True iff some triangle passes the closest-hit query's leaf test with t_near < t < t_far.  At t_near = 0 this is
+        `hit & (t_hit < t_far)` of trace_shade(return_hits=True), bit for bit, from a traversal that stops at the first accepted triangle.  t_far = nan
+        or <= t_near: nothing is occluded.  out: a bool or uint8 [R] device tensor to write into.  stats=True: also int64 [1] = the occluded rays"""
+        org = _dev_f32(org, self.device).reshape(-1, 3)
+        dir = _dev_f32(dir, self.device).reshape(-1, 3)
+        R = org.shape[0]
+        if dir.shape[0] != R:
+            raise ValueError("test_occlusions: %d origins, %d directions" % (R, dir.shape[0]))
+        if out is None:
+            out = torch.zeros(R, device=self.device, dtype=torch.bool)
+        elif tuple(out.shape) != (R,) or out.dtype not in (torch.bool, torch.uint8) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous bool or uint8 [%d] on %s" % (R, self.device))
+        st = torch.zeros(1, device=self.device, dtype=torch.int64) if stats else None
+        if R > 0:
+            _lib.check(_lib.lib().texir_trace_occluded(self.h, _lib.ptr(org), _lib.ptr(dir), R, float(t_near), float(t_far), _lib.ptr(out), _lib.ptr(st),
+                                                       _lib.stream_ptr()))
+        return (out, st) if stats else out
+
     # -- TracerO3d.forward hot loop (tracer_o3d_irt.py:156-178) -------------------------------------------
     def irt_generate(self, pos, nrm, shift, n_samples, mode="uniform", texel_ids=None, out=None, stats=False):
         pos = _dev_f32(pos, self.device).reshape(-1, 3)
@@ -198,12 +228,14 @@ class Scene:
         return out
 
     # -- inserted emitters (include/texir_hip.h texir_irt_lights) ------------------------------------------
-    def irt_lights(self, pos, nrm, shift, lights, n_samples, texel_ids=None, t_max=0.999, out=None, stats=False):
+    def irt_lights(self, pos, nrm, shift, lights, n_samples, texel_ids=None, t_max=0.999, out=None, stats=False, query="closest"):
         """direct irradiance factors of inserted area lights: lights [K,16] float32 records (irtlight.pack; a device tensor is used in place, so a
         recorded graph replays with whatever the records hold then), K <= 8 -> F [K, Nt]; the irradiance under emitted radiance c_k is c_k * F[k]
         (irtlight.add).  Any point list: texels or a view's pixels.  t_max: the ray is occluded iff its closest hit has t < t_max in units of the
         segment to the sample point (0.999: a light laid onto a surface is not shadowed by it).  Only listed texels are written.
-        stats=True: also int64 [2] = (rays traced, visible ones)"""
+        stats=True: also int64 [2] = (rays traced, visible ones).  query: 'closest' | 'any' (texir_irt_lights_any: visibility as an occlusion query, the
+        same bits)"""
+        call = "texir_irt_lights_any" if check_query(query) else "texir_irt_lights"
         pos = _dev_f32(pos, self.device).reshape(-1, 3)
         nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
         Nt = pos.shape[0]
@@ -224,9 +256,9 @@ class Scene:
         st = torch.zeros(2, device=self.device, dtype=torch.int64) if stats else None
         empty = Nt == 0 or (texel_ids is not None and n_ids == 0)          # (an EMPTY id list must not reach the library as "no list = all texels")
         if not empty:
-            _lib.check(_lib.lib().texir_irt_lights(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(ids), n_ids, Nt,
-                                                   _lib.ptr(lights) if K else None, K, int(n_samples), float(t_max), _lib.ptr(out) if K else None, _lib.ptr(st),
-                                                   _lib.stream_ptr()))
+            _lib.check(getattr(_lib.lib(), call)(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(ids), n_ids, Nt,
+                                                 _lib.ptr(lights) if K else None, K, int(n_samples), float(t_max), _lib.ptr(out) if K else None, _lib.ptr(st),
+                                                 _lib.stream_ptr()))
         return (out, st) if stats else out
 
 

@@ -23,12 +23,13 @@ The texel G-buffer of any uv-mapped mesh (position + 1e-2 * normal, normal; zero
 device (gbuffer.raster_texel_gbuffer) and written in the format train.texel_gbuffer = file reads.  <res> is the atlas size, or HxW.
 
     python -m texir_code_amd.tools bake-atlas <root> <res|HxW> [--out DIR] [--cos-min X] [--normal geometric|shading] [--seg]
-                                              [--fill] [--fill-dist D] [--fill-cos C]
+                                              [--fill] [--fill-dist D] [--fill-cos C] [--query closest|any]
 
 The radiance atlas hdr_texture.hdr and the index texture 0.png of <root>/vrproc/hdr_texture/out1.obj from the calibrated panoramas hdr/<id>/ccm.hdr
 (info/aligned.txt, info/final_extrinsics.txt; the alpha of derived/<id>/panoImage_orig.jpg masks invalid pixels when it exists), selected per texel on the
 device (atlas.bake_atlas, csrc/texbake.hip), written into DIR (default <root>/vrproc/hdr_texture/baked; existing files are not overwritten).  --seg adds
-0_seg_gray.png gathered from derived/<id>/panoImage_gray.png.
+0_seg_gray.png gathered from derived/<id>/panoImage_gray.png.  --query any puts the segment test to the occlusion query (texir_atlas_bake_any) instead of a
+closest-hit query (the default, closest): the files are the same, byte for byte.
 
 --fill completes the atlas (atlas.fill_atlas, csrc/texfill.hip): a covered texel no panorama sees takes the radiance of the nearest OBSERVED texel in world
 space within D scene units (--fill-dist, default 0.5: the depth of what stands on an indoor floor -- a choice, not a measurement) whose normal agrees with
@@ -134,8 +135,8 @@ def write_texel_gbuffer(path_obj, H, W, dst, normal="geometric", device=0):
 
 
 def parse_bake_atlas(argv):
-    """the arguments after `bake-atlas` -> dict(root, H, W, out, cos_min, normal, seg, fill, fill_dist, fill_cos); ValueError names what is wrong"""
-    opt = {"--out": None, "--cos-min": "0.1", "--normal": "geometric", "--fill-dist": "0.5", "--fill-cos": "0.5"}
+    """the arguments after `bake-atlas` -> dict(root, H, W, out, cos_min, normal, seg, fill, fill_dist, fill_cos, query); ValueError names what is wrong"""
+    opt = {"--out": None, "--cos-min": "0.1", "--normal": "geometric", "--fill-dist": "0.5", "--fill-cos": "0.5", "--query": "closest"}
     flags, rest = [], []
     it = iter(argv)
     for a in it:
@@ -156,6 +157,8 @@ def parse_bake_atlas(argv):
         raise ValueError("<res> must be an integer or HxW and --cos-min a number, got %r, %r" % (rest[1], opt["--cos-min"]))
     if opt["--normal"] not in ("geometric", "shading"):
         raise ValueError("--normal must be geometric or shading")
+    if opt["--query"] not in ("closest", "any"):
+        raise ValueError("--query must be closest or any, got %r" % (opt["--query"],))
     try:
         fd, fc = float(opt["--fill-dist"]), float(opt["--fill-cos"])
     except (ValueError, TypeError):
@@ -165,7 +168,7 @@ def parse_bake_atlas(argv):
     if not 0.0 <= fc <= 1.0:
         raise ValueError("--fill-cos must be in [0, 1], got %r" % fc)
     return {"root": rest[0], "H": H, "W": W, "out": opt["--out"], "cos_min": cm, "normal": opt["--normal"], "seg": "--seg" in flags, "fill": "--fill" in flags,
-            "fill_dist": fd, "fill_cos": fc}
+            "fill_dist": fd, "fill_cos": fc, "query": opt["--query"]}
 
 
 def relight_irt(directory, k, colour, replace=False):
@@ -300,7 +303,7 @@ def main(argv):
             return 2
         try:
             res = atlas.bake_files(o["root"], o["H"], o["W"], o["out"], o["cos_min"], o["normal"], o["seg"], fill=o["fill"], fill_dist=o["fill_dist"],
-                                   fill_cos=o["fill_cos"])
+                                   fill_cos=o["fill_cos"], query=o["query"])
         except FileExistsError as e:
             print(e)
             return 1
