@@ -45,7 +45,6 @@ static bool find4(const BvhHost& h, int32_t node, const float* p, uint32_t prim)
         if (c >= 0) { if (find4(h, c, p, prim)) return true; }
         else {
             const uint32_t code = (uint32_t)~c; const uint32_t first = code >> 3, cnt = (code & 7u) + 1;
-#if TEXIR_QUAD
             // the 4-wide tree names quad records: record r owns slots 2 r, 2 r + 1, and its four vertices are those of its two stored triangles
             for (uint32_t r = first; r < first + cnt; r++) {
                 const GpuQuad& q = h.quads[r]; const GpuTri& a = h.tris[2 * r]; const GpuTri& b = h.tris[2 * r + 1];
@@ -54,9 +53,6 @@ static bool find4(const BvhHost& h, int32_t node, const float* p, uint32_t prim)
                                                         : (!std::memcmp(q.q + 9, b.v0, 12) && !std::memcmp(q.q + 6, b.e1, 12) && !std::memcmp(q.q + 3, b.e2, 12)));
                 if (geo && (a.prim == prim || b.prim == prim)) return true;
             }
-#else
-            for (uint32_t i = 0; i < cnt; i++) if (h.tris[first + i].prim == prim) return true;
-#endif
         }
     }
     return false;

@@ -34,7 +34,7 @@ struct Tmp {
     Box box;
     int first = 0, count = 0;           // leaf payload: a run of `order`
     int slot_first = 0, slot_count = 0; // ... as leaf-order slots (assign_slots)
-    int rec_first = 0, rec_count = 0;   // ... as quad records (TEXIR_QUAD)
+    int rec_first = 0, rec_count = 0;   // ... as quad records
     std::unique_ptr<Tmp> l, r;
     int depth_below = 0;
 };
@@ -51,13 +51,9 @@ constexpr int kBins = 32;
 static int max_leaf()
 {
     const int v = env().max_leaf ? env().max_leaf : kMaxLeaf;
-#if TEXIR_QUAD
     // quad records own two leaf-order slots each: a leaf of n unpaired triangles spans up to 2 n - 1 slots, and the binary tree's leaf code has 3 bits
     // for (slots - 1) -- more than 4 triangles per leaf would spill into the first-slot field (the deep-tree fallback and TEXIR_BVH_WIDTH=2 read it)
     return std::min(v, 4);
-#else
-    return v;
-#endif
 }
 
 std::unique_ptr<Tmp> build(const Ctx& c, int first, int count, int depth, int par_levels)
@@ -130,7 +126,7 @@ std::unique_ptr<Tmp> build(const Ctx& c, int first, int count, int depth, int pa
     return n;
 }
 
-// leaf codes (bvh_build.h): the binary tree names leaf-order slots, the 4-wide tree names quad records when the library has them
+// leaf codes (bvh_build.h): the binary tree names leaf-order slots, the 4-wide tree names quad records
 inline int32_t leaf_code(const Tmp* t)
 {
     // (cannot fire with TEXIR_MAX_LEAF <= 8; thrown -- texir_scene_create turns it into TEXIR_ERR_INVALID -- rather than aborting the host process)
@@ -139,11 +135,7 @@ inline int32_t leaf_code(const Tmp* t)
 }
 inline int32_t leaf_code4(const Tmp* t)
 {
-#if TEXIR_QUAD
     return ~(int32_t)(((uint32_t)t->rec_first << 3) | (uint32_t)(t->rec_count - 1));
-#else
-    return leaf_code(t);
-#endif
 }
 
 void put_box(GpuNode& g, int slot, const Box& b)
@@ -338,22 +330,17 @@ void build_bvh(const float* verts, int V, const int32_t* tris, int T, const floa
         auto vtx = [&](int p, int k) { return verts + 3 * (size_t)tris[3 * (size_t)p + k]; };
         auto same = [&](const float* a, const float* b) { return std::memcmp(a, b, 3 * sizeof(float)) == 0; };
         auto pair_up = [&](int p, int q, int& r0, int& r1) {
-#if TEXIR_QUAD
             for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++)
                 if (same(vtx(p, i), vtx(q, (j + 1) % 3)) && same(vtx(p, (i + 1) % 3), vtx(q, j))) {
                     // degenerate partners (a repeated vertex) stay single: their "shared edge" is not one
                     if (same(vtx(p, i), vtx(p, (i + 1) % 3)) || same(vtx(p, (i + 2) % 3), vtx(q, (j + 2) % 3))) return false;
-#if TEXIR_UV_QUAD
                     // one uv per record corner: a uv seam along the shared edge keeps the two triangles single
                     if (tri_uvs) {
                         auto cuv = [&](int t_, int k) { return tri_uvs + 6 * (size_t)t_ + 2 * (size_t)k; };
                         if (std::memcmp(cuv(p, i), cuv(q, (j + 1) % 3), 8) || std::memcmp(cuv(p, (i + 1) % 3), cuv(q, j), 8)) return false;
                     }
-#endif
                     r0 = (i + 2) % 3; r1 = (j + 2) % 3; return true;
                 }
-#endif
-            (void)p; (void)q; (void)r0; (void)r1;
             return false;
         };
         std::vector<Tmp*> stack{root.get()};
@@ -363,7 +350,7 @@ void build_bvh(const float* verts, int V, const int32_t* tris, int T, const floa
             t->rec_first = (int)recs.size();
             bool last_single = false;
             // (leaves of more than two triangles, TEXIR_MAX_LEAF: bring partners next to each other first -- the order inside a leaf is free)
-            if (TEXIR_QUAD && t->count > 2)
+            if (t->count > 2)
                 for (int i = t->first; i + 1 < t->first + t->count; i++) {
                     int r0, r1, j = i + 1;
                     while (j < t->first + t->count && !pair_up(order[i], order[j], r0, r1)) j++;
@@ -371,21 +358,15 @@ void build_bvh(const float* verts, int V, const int32_t* tris, int T, const floa
                 }
             for (int i = t->first; i < t->first + t->count;) {
                 int r0 = 0, r1 = 0;
-                if (TEXIR_QUAD && i + 1 < t->first + t->count && pair_up(order[i], order[i + 1], r0, r1)) { recs.push_back(Rec{order[i], r0, order[i + 1], r1}); i += 2; last_single = false; }
-                else if (TEXIR_QUAD) { recs.push_back(Rec{order[i], 0, -1, 0}); i += 1; last_single = true; }
-                else { recs.push_back(Rec{order[i], 0, -1, 0}); i += 1; }
+                if (i + 1 < t->first + t->count && pair_up(order[i], order[i + 1], r0, r1)) { recs.push_back(Rec{order[i], r0, order[i + 1], r1}); i += 2; last_single = false; }
+                else { recs.push_back(Rec{order[i], 0, -1, 0}); i += 1; last_single = true; }
             }
             t->rec_count = (int)recs.size() - t->rec_first;
-#if TEXIR_QUAD
             t->slot_first = 2 * t->rec_first; t->slot_count = 2 * t->rec_count - (last_single ? 1 : 0);
-#else
-            (void)last_single;
-            t->slot_first = t->rec_first; t->slot_count = t->rec_count;
-#endif
         }
     }
     const size_t n_rec = recs.size();
-    const size_t n_slots = TEXIR_QUAD ? 2 * n_rec : n_rec;
+    const size_t n_slots = 2 * n_rec;
     out.n_slots = (int64_t)n_slots;
 
     out.nodes.clear();
@@ -408,29 +389,24 @@ void build_bvh(const float* verts, int V, const int32_t* tris, int T, const floa
     out.nodes4.reserve((size_t)T / 2 + 16);
     out.nodes4f.clear();
     out.nodes4f.reserve((size_t)T / 2 + 16);
-    // the slot (quad libraries: the record) after the last one holds a degenerate all-zero triangle (record): the target of unused child slots
-    Emit4Ctx cx{slack, &out.nodes4, &out.nodes4f, ~(int32_t)(((uint32_t)(TEXIR_QUAD ? n_rec : n_slots) << 3) | 0u), 0};
+    // the slot and the record after the last one hold a degenerate all-zero triangle / record: the target of unused child slots
+    Emit4Ctx cx{slack, &out.nodes4, &out.nodes4f, ~(int32_t)(((uint32_t)n_rec << 3) | 0u), 0};
     emit4(root.get(), cx, 1);
     out.max_depth4 = cx.max_depth;
     relayout4(out.nodes4, out.nodes4f, env().bvh_layout);
     // slot data in STORED corner order: stored corner k = the caller's corner (rot + k) % 3
     out.tris.assign(n_slots + 1, GpuTri{});
-    out.uvs.assign((TEXIR_UV_QUAD ? n_rec : n_slots) + 1, GpuTriUV{});
+    out.uvs.assign(n_rec + 1, GpuTriUV{});
     for (auto& g : out.tris) g.prim = 0xFFFFFFFFu;          // holes (the odd slot of a single) and the dummy: degenerate, never hit
     auto put_slot = [&](size_t slot, int p, int rot) {
         GpuTri& g = out.tris[slot];
         const float* v[3];
         for (int k = 0; k < 3; k++) v[k] = verts + 3 * (size_t)tris[3 * (size_t)p + (rot + k) % 3];
-#if TEXIR_TRI_WATERTIGHT
         for (int k = 0; k < 3; k++) { g.v0[k] = v[0][k]; g.e1[k] = v[1][k]; g.e2[k] = v[2][k]; }         // the vertices themselves, bit for bit
-#else
-        for (int k = 0; k < 3; k++) { g.v0[k] = v[0][k]; g.e1[k] = v[1][k] - v[0][k]; g.e2[k] = v[2][k] - v[0][k]; }
-#endif
         g.prim = (uint32_t)p;
         const uint32_t r = (uint32_t)rot;
         std::memcpy(&g.pad1, &r, 4); g.pad2 = 0.f;
-#if TEXIR_UV_QUAD
-        // record form: the even slot writes its three stored corners (q0, q1, q2), the odd slot its first stored corner (q3; its other two are q2, q1)
+        // the even slot writes its three stored corners (q0, q1, q2), the odd slot its first stored corner (q3; its other two are q2, q1)
         GpuTriUV& u = out.uvs[slot >> 1];
         const int n_put = (slot & 1) ? 1 : 3;
         for (int k = 0; k < n_put; k++) {
@@ -438,13 +414,7 @@ void build_bvh(const float* verts, int V, const int32_t* tris, int T, const floa
             const int at = (slot & 1) ? 3 : k;
             u.uv[2 * at] = uv[0]; u.uv[2 * at + 1] = uv[1];
         }
-#else
-        GpuTriUV& u = out.uvs[slot];
-        for (int k = 0; k < 3; k++) { const float* uv = tri_uvs + 6 * (size_t)p + 2 * (size_t)((rot + k) % 3); u.uv[2 * k] = uv[0]; u.uv[2 * k + 1] = uv[1]; }
-        u.uv[6] = u.uv[7] = 0.f;
-#endif
     };
-#if TEXIR_QUAD
     out.quads.assign(n_rec + 1, GpuQuad{});
     for (size_t r = 0; r < n_rec; r++) {
         const Rec& rc = recs[r];
@@ -456,9 +426,6 @@ void build_bvh(const float* verts, int V, const int32_t* tris, int T, const floa
         // (q3: the partner's first stored corner -- its other two are q2, q1 by construction; a single repeats q2: a triangle without area)
         for (int k = 0; k < 3; k++) q.q[9 + k] = rc.p1 >= 0 ? out.tris[2 * r + 1].v0[k] : a.e2[k];
     }
-#else
-    for (size_t r = 0; r < n_rec; r++) put_slot(r, recs[r].p0, 0);
-#endif
 }
 
 }  // namespace texir

@@ -17,16 +17,12 @@ struct alignas(16) GpuNode {
 };
 static_assert(sizeof(GpuNode) == 64, "node must be 64 bytes");
 
-// Triangle intersector (compile-time, the builder and the kernels of one library agree):
-//   TEXIR_TRI_WATERTIGHT = 1 (default): edge functions in ray space on the three stored VERTICES (the Pluecker form Embree's
-//     robust mode uses): the value a ray gets for an edge shared by two triangles is exactly the negative of the neighbour's,
-//     so no ray slips between them;  = 0: Moeller-Trumbore on (v0, e1, e2), ~30 VALU cheaper per test, leaks at shared edges.
-#ifndef TEXIR_TRI_WATERTIGHT
-#define TEXIR_TRI_WATERTIGHT 1
-#endif
+// Triangle intersector: edge functions in ray space on the three stored VERTICES (the Pluecker form Embree's robust mode uses): the
+// value a ray gets for an edge shared by two triangles is exactly the negative of the neighbour's, so no ray slips between them.
+// (Moeller-Trumbore on (v0, e1, e2) is ~30 VALU cheaper per test and leaks at shared edges.)
 
-// 48-byte triangle (v0, prim), (a, 0), (b, 0) with (a, b) = (v1, v2) [watertight] or (e1, e2) = (v1-v0, v2-v0), + a separate 32-byte uv
-// record fetched only for the closest hit.  (A 64-byte record carrying the uvs measured -2 %: tools/experiments/.)
+// 48-byte triangle (v0, prim), (v1, rot), (v2, 0) -- the fields e1, e2 hold the VERTICES v1, v2, not edges -- + a separate uv record fetched only for
+// the closest hit.  (A 64-byte record carrying the uvs measured -2 %: tools/experiments/.)
 struct alignas(16) GpuTri {
     float v0[3]; uint32_t prim;
     float e1[3]; float pad1;
@@ -35,7 +31,7 @@ struct alignas(16) GpuTri {
 static_assert(sizeof(GpuTri) == 48, "triangle must be 48 bytes");
 constexpr int kTriQuads = 3;          // float4s per triangle record
 
-// Quad leaves (TEXIR_QUAD = 1, default; watertight intersector only): the two triangles of a leaf that share an edge -- in a tessellated mesh nearly every
+// Quad leaves: the two triangles of a leaf that share an edge -- in a tessellated mesh nearly every
 // 2-triangle leaf -- are stored as ONE 48-byte record of their four vertices (q0, q1, q2, q3): triangle 0 = (q0, q1, q2), triangle 1 = (q3, q2, q1), the
 // shared edge being (q1, q2).  The 4-wide traversal fetches three 16-byte words per leaf record instead of six 12-byte vertices per pair, shears four
 // vertices instead of six and evaluates five edge functions instead of six (the shared edge's value is the neighbour's negated, exactly).
@@ -46,21 +42,13 @@ constexpr int kTriQuads = 3;          // float4s per triangle record
 //   corner (rot + k) % 3), and only a barycentric that leaves the library (texir_trace_shade's primitive uvs) is turned back.
 //   Leaf codes: the binary tree's name slots (first slot << 3 | slots - 1: a dummy slot in the range is tested and never hit), the 4-wide tree's name
 //   records (first record << 3 | records - 1).
-#ifndef TEXIR_QUAD
-#define TEXIR_QUAD TEXIR_TRI_WATERTIGHT
-#endif
 struct alignas(16) GpuQuad { float q[12]; };          // q0.xyz q1.xyz q2.xyz q3.xyz
 static_assert(sizeof(GpuQuad) == 48, "quad record must be 48 bytes");
 
-// Corner uvs, fetched only for the closest hit.
-//   TEXIR_UV_QUAD = 1 (default with quad leaves): ONE 32-byte record per quad RECORD -- the uvs of its four vertices (q0, q1, q2, q3); triangle 0 (even slot)
-//     reads (q0, q1, q2), triangle 1 (odd slot) reads (q3, q2, q1), the stored corner order of its slot.  Two triangles are only paired when their corner uvs
-//     agree on the shared edge (no uv seam along it), so the four pairs are all there is.  Half the bytes of the per-slot form: a 128-byte line holds the
-//     uvs of 8 neighbouring triangles instead of 4 (the hit shader's uv fetch was 1 of its 2 lines per ray; round 5).
-//   TEXIR_UV_QUAD = 0: 32 bytes per leaf-order SLOT: (uv0, uv1), (uv2, 0, 0).
-#ifndef TEXIR_UV_QUAD
-#define TEXIR_UV_QUAD TEXIR_QUAD
-#endif
+// Corner uvs, fetched only for the closest hit: ONE 32-byte record per quad RECORD -- the uvs of its four vertices (q0, q1, q2, q3); triangle 0 (even slot)
+// reads (q0, q1, q2), triangle 1 (odd slot) reads (q3, q2, q1), the stored corner order of its slot.  Two triangles are only paired when their corner uvs
+// agree on the shared edge (no uv seam along it), so the four pairs are all there is.  Half the bytes of a record per leaf-order slot ((uv0, uv1),
+// (uv2, 0, 0)): a 128-byte line holds the uvs of 8 neighbouring triangles instead of 4 (the hit shader's uv fetch was 1 of its 2 lines per ray; round 5).
 struct alignas(16) GpuTriUV {
     float uv[8];
 };
@@ -100,9 +88,9 @@ struct BvhHost {
     std::vector<GpuNode4> nodes4;
     std::vector<GpuNode4F> nodes4f;     // index-for-index with nodes4
     std::vector<GpuTri> tris;           // by leaf-order slot (+ one degenerate dummy at the end)
-    std::vector<GpuTriUV> uvs;
-    std::vector<GpuQuad> quads;         // TEXIR_QUAD: by record (+ one all-zero dummy at the end); record r owns slots 2 r, 2 r + 1
-    int64_t n_slots = 0;                // leaf-order slots (= triangles without TEXIR_QUAD)
+    std::vector<GpuTriUV> uvs;          // by record
+    std::vector<GpuQuad> quads;         // by record (+ one all-zero dummy at the end); record r owns slots 2 r, 2 r + 1
+    int64_t n_slots = 0;                // leaf-order slots (2 per record)
     int max_depth = 0, max_depth4 = 0;
 };
 

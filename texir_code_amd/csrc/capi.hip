@@ -29,7 +29,7 @@ struct texir_scene {
     size_t packed_bytes = 0;
     int packed_layout = 0;
     unsigned int* d_tex_flag = nullptr;  // device word: texels of the last pack that were not representable
-    int64_t n_nodes = 0, n_nodes4 = 0, n_tris = 0, n_slots = 0 /* leaf-order slots behind d_tris / d_uvs / d_cnrm: = n_tris, or 2 per quad record (bvh_build.h) */, n_quads = 0, n_uv_recs = 0 /* 32-byte uv records behind d_uvs: one per quad record (TEXIR_UV_QUAD) or per slot */, max_depth = 0;
+    int64_t n_nodes = 0, n_nodes4 = 0, n_tris = 0, n_slots = 0 /* leaf-order slots behind d_tris / d_uvs / d_cnrm: 2 per quad record (bvh_build.h) */, n_quads = 0, n_uv_recs = 0 /* 32-byte uv records behind d_uvs: one per quad record */, max_depth = 0;
     int width = 2;
     size_t tex_bytes = 0;
     std::vector<uint32_t> slot_prim;     // leaf slot -> primitive id (host copy, for per-corner attribute uploads; 0xFFFFFFFF: an empty slot)
@@ -43,7 +43,7 @@ struct texir_scene {
     static constexpr int kWorkSlots = 64;
     unsigned long long* d_work = nullptr;
     mutable std::atomic<unsigned> work_next{0};      // (launching on an immutable scene still advances the slot)
-    // phase-scheduler weight of this scene (device_common.h TEXIR_SCHED): decided once by texir_scene_tune, read by every tracing launch
+    // phase-scheduler weight of this scene (device_common.h kSchedNodeWeight): decided once by texir_scene_tune, read by every tracing launch
     mutable std::atomic<int> sched_state{0};         // 0 undecided, 1 being decided, 2 decided
     mutable std::atomic<int> sched_weight{0};        // 0 = the compile-time default (2)
     mutable std::atomic<double> node_utilisation{-1.0};   // what the decision measured (texir_scene_scheduler)

@@ -18,7 +18,7 @@ struct SceneDev {
                            // node steps; null = every node step per lane (TEXIR_UNIFORM_FLOAT=0)
     const float4* nodes;   // GpuNode as 4 x float4
     const float4* tris;    // GpuTri as kTriQuads x float4, by leaf-order slot
-    const float4* quads;   // GpuQuad as 3 x float4, by record (TEXIR_QUAD: what the 4-wide tree's leaves name; record r owns slots 2 r, 2 r + 1)
+    const float4* quads;   // GpuQuad as 3 x float4, by record (what the 4-wide tree's leaves name; record r owns slots 2 r, 2 r + 1)
     const float4* uvs;     // GpuTriUV as 2 x float4
     const float* tex;      // [Ht,Wt,3] row-major (layout 0), or the retiled copy the hit shader reads (layouts 1, 2: see shade_hit)
     int Ht, Wt;
@@ -40,27 +40,10 @@ constexpr int kStackCap = 96;        // LDS part + private overflow; the host ch
 // scalar node path took the L1 off the critical path (8-byte entries): 6 waves / 12 entries 15.01, 7 / 11 15.82, 8 / 10 15.87 (c2: 16.30, 17.11, 17.40;
 // c4_scan: 4.98, 5.31, 5.54): 8 waves per SIMD = 64 VGPRs (the compiler parks the per-texel frame and the ray's shear rows in scratch across the
 // traversal loop) and a 10-entry LDS stack.
-#ifndef TEXIR_CULL
-#define TEXIR_CULL 1                                    // stack entries carry the child's entry distance (StackEntry below)
-#endif
-constexpr bool kCull = TEXIR_CULL != 0;
-#ifndef TEXIR_GROUP_LSTK
-#define TEXIR_GROUP_LSTK (TEXIR_CULL ? 10 : 16)         // 8-byte entries with culling: 10 x 2 KiB = 20 KiB per block, 8 blocks = all 160 KiB of a CU
-#endif
-constexpr int kGroupLstk = TEXIR_GROUP_LSTK;            // the IrT kernels (irt_kernel, irt_group_kernel, irt_stream_kernel, irt_split_kernel)
-#ifndef TEXIR_GROUP_WAVES
-#define TEXIR_GROUP_WAVES 8
-#endif
-constexpr int kGroupWaves = TEXIR_GROUP_WAVES;
-constexpr int kLstk = kCull ? kLdsStack / 2 : kLdsStack;   // the single-ray tracing kernels: 24 KiB of stack per block either way
-// which cells a part of a texel's passes holds: 1 = an azimuthal wedge (wedge_cell below), 0 = a ring of elevations
-#ifndef TEXIR_PART_WEDGE
-#define TEXIR_PART_WEDGE 1
-#endif
-// azimuth sine / cosine of the fused IrT sampling from v_sin_f32 / v_cos_f32 (sample_dir<FAST>)
-#ifndef TEXIR_IRT_FAST_SINCOS
-#define TEXIR_IRT_FAST_SINCOS 0
-#endif
+// Stack entries are 8 bytes (child code + the child's entry distance, see trace_core): 10 x 2 KiB = 20 KiB per block, 8 blocks = all 160 KiB of a CU.
+constexpr int kGroupLstk = 10;                          // the IrT kernels (irt_kernel, irt_group_kernel, irt_stream_kernel, irt_split_kernel)
+constexpr int kGroupWaves = 8;
+constexpr int kLstk = kLdsStack / 2;                    // the single-ray tracing kernels: 24 KiB of stack per block
 
 // ------------------------------------------------------------------------------------------------
 // sampling -- kept free of fused multiply-adds so that it tracks the reference's separately rounded
@@ -118,22 +101,14 @@ __device__ __forceinline__ void polar(int mode, float s0, float rough, float& ct
     }
 }
 
-// FAST (the fused IrT kernels only; texir_generate_dir and the GGX kernels keep the libm form that is pinned at 5e-6 on the reference's
-// own directions): sin / cos of phi = 2 pi s1 - pi from the hardware's v_sin_f32 / v_cos_f32, which take their argument in revolutions --
-// sin(2 pi s1 - pi) = -sin(2 pi s1), no range reduction, 2 quarter-rate instructions instead of ~70 -- absolute error ~1e-6 per component,
-// two orders of magnitude inside the 2e-5 the whole-loop golden test allows.
-template <bool FAST = false>
+// (sin / cos of phi from libm's sincosf, ~70 instructions: the form that is pinned at 5e-6 on the reference's own directions)
 __device__ __forceinline__ void sample_dir(int mode, float s0, float s1, float rough, const Frame& f, float* L)
 {
     float ct, st;
     polar(mode, s0, rough, ct, st);
     float sp, cp;
-    if constexpr (FAST) {
-        sp = -__builtin_amdgcn_sinf(s1); cp = -__builtin_amdgcn_cosf(s1);
-    } else {
-        float phi = 6.283185307179586f * s1 - 3.141592653589793f;
-        sincosf(phi, &sp, &cp);
-    }
+    float phi = 6.283185307179586f * s1 - 3.141592653589793f;
+    sincosf(phi, &sp, &cp);
     sp = sp * st; cp = -(cp * st);
     for (int a = 0; a < 3; a++) L[a] = f.V[a] * sp + f.n[a] * ct + f.U[a] * cp;
 }
@@ -141,16 +116,12 @@ __device__ __forceinline__ void sample_dir(int mode, float s0, float s1, float r
 // corner uvs of the triangle in leaf slot `slot`: a = (uv0, uv1), b = (uv2, -, -)
 __device__ __forceinline__ void tri_uvs(const SceneDev& sc, int slot, float4& a, float4& b)
 {
-#if TEXIR_UV_QUAD
     // one 32-byte record per quad record: (q0, q1), (q2, q3); the even slot is triangle (q0, q1, q2), the odd one (q3, q2, q1)  (bvh_build.h)
     const size_t rec = (size_t)(slot >> 1);
     const float4 A = sc.uvs[2 * rec], B = sc.uvs[2 * rec + 1];
     const bool odd = (slot & 1) != 0;
     a = odd ? make_float4(B.z, B.w, B.x, B.y) : A;
     b = odd ? make_float4(A.z, A.w, 0.f, 0.f) : B;
-#else
-    a = sc.uvs[2 * (size_t)slot]; b = sc.uvs[2 * (size_t)slot + 1];
-#endif
 }
 // primitive id (row of the caller's index array) of the triangle in leaf slot `slot`
 __device__ __forceinline__ uint32_t tri_prim(const SceneDev& sc, int slot) { return __float_as_uint(sc.tris[3 * (size_t)slot].w); }
@@ -323,44 +294,27 @@ constexpr uint32_t kProbeEvery = TEXIR_PROBE_EVERY;
 // wave_iters[2 + ...]: steps, timed steps, cycles of timed steps -- of per-lane node steps, wave-uniform node steps, leaf steps; then timed empty regions, their cycles
 constexpr int kProbeSlots = 11;
 
-// TEXIR_SCHED (A/B switch; 1 = default).  How the wave shares its issue slots between lanes that hold an inner node and lanes
-// that hold a leaf:
-//   0: "while-while" -- node steps until NO lane holds an inner node, then leaf steps until NO lane holds a leaf.  One lane on a
-//      long run of inner nodes keeps 63 lanes waiting at their leaves: on cluttered scenes the wave executes 2.8x the node steps of
-//      its average ray (c4_scan: 55 wave-level node steps per pass for 19.7 per ray, of which only 30 are the slowest lane's).
-//   1: per step, ballot + population count of both kinds of lanes and the body with more lanes waiting runs; node lanes count
-//      w-fold (a leaf step -- 1 or 2 watertight triangle tests and the culling pop -- costs ~1.5 node steps, and on coherent scenes leaf lanes
-//      arrive in bursts that are worth a short wait).  Every lane still performs exactly the same node visits, triangle tests and stack
-//      operations in the same order (the schedule only decides WHEN a lane's next step issues), so hits are identical bit for bit.
-//      CPU replay of the kernel's schedule (tools/bvh_sim.cpp): c4_scan 55.3 -> 36.8 (w = 1) / 40.6 (w = 2) wave-level node steps per pass,
-//      c4 19.5 -> 17.6 / 17.8.  Measured (profiles/r03/ab_tables.txt; Grays/s, while-while = 1): w = 1: c4_scan 1.28, c4 0.98 (the leaf
-//      batches get smaller: wave-level triangle steps 5.2 -> 7.1); w = 2: c4_scan 1.24, c4 1.00; w = 3: 1.19, 1.00.
-//      w comes with the scene (SceneDev::sched_weight): kSchedNodeWeight = 2 unless texir_scene_tune has measured that the scene's node steps
-//      run less than 60 % full (cluttered scenes), then 1.
-#ifndef TEXIR_SCHED
-#define TEXIR_SCHED 1
-#endif
-// leaf steps specialised for the wave's common dominant ray axis (A/B switch; 0 = every leaf step selects the components per lane)
-#ifndef TEXIR_LEAF_UNIFORM_KZ
-#define TEXIR_LEAF_UNIFORM_KZ 1
-#endif
-#ifndef TEXIR_SCHED_NODE_WEIGHT
-#define TEXIR_SCHED_NODE_WEIGHT 2
-#endif
-constexpr int kSchedNodeWeight = TEXIR_SCHED_NODE_WEIGHT;
-// TEXIR_STACK_DRAIN2 (A/B switch; 1 = default): the culling pop of the all-in-LDS paths (trace_core's pop_lds) examines two stack entries per LDS round trip.
-#ifndef TEXIR_STACK_DRAIN2
-#define TEXIR_STACK_DRAIN2 1
-#endif
+// How the wave shares its issue slots between lanes that hold an inner node and lanes that hold a leaf: per step, ballot + population
+// count of both kinds of lanes and the body with more lanes waiting runs; node lanes count w-fold (a leaf step -- 1 or 2 watertight triangle
+// tests and the culling pop -- costs ~1.5 node steps, and on coherent scenes leaf lanes arrive in bursts that are worth a short wait).
+// Every lane performs exactly the same node visits, triangle tests and stack operations in the same order as under any other schedule
+// (the schedule only decides WHEN a lane's next step issues), so hits do not depend on it, bit for bit.
+//   What it replaced was a "while-while" loop -- node steps until NO lane holds an inner node, then leaf steps until NO lane holds a leaf.
+// There one lane on a long run of inner nodes keeps 63 lanes waiting at their leaves: on cluttered scenes the wave executes 2.8x the node
+// steps of its average ray (c4_scan: 55 wave-level node steps per pass for 19.7 per ray, of which only 30 are the slowest lane's).
+// CPU replay of the kernel's schedule (tools/bvh_sim.cpp): c4_scan 55.3 -> 36.8 (w = 1) / 40.6 (w = 2) wave-level node steps per pass,
+// c4 19.5 -> 17.6 / 17.8.  Measured (profiles/r03/ab_tables.txt; Grays/s, while-while = 1): w = 1: c4_scan 1.28, c4 0.98 (the leaf
+// batches get smaller: wave-level triangle steps 5.2 -> 7.1); w = 2: c4_scan 1.24, c4 1.00; w = 3: 1.19, 1.00.
+// w comes with the scene (SceneDev::sched_weight): kSchedNodeWeight = 2 unless texir_scene_tune has measured that the scene's node steps
+// run less than 60 % full (cluttered scenes), then 1.
+constexpr int kSchedNodeWeight = 2;
 // wave_iters[kWiCulled / kWiOverflow] (STATS; per LANE, unlike the wave-level slots before them): stats[6] and stats[7] of include/texir_hip.h
 constexpr int kWiCulled = 2 + kProbeSlots, kWiOverflow = 3 + kProbeSlots, kWiSlots = 4 + kProbeSlots;
 
-// CULL: a stack entry also carries the child's entry distance, and an entry whose distance is not below the closest hit found
+// Culling: a stack entry also carries the child's entry distance, and an entry whose distance is not below the closest hit found
 // since it was pushed is dropped when it is popped (it cannot contain a closer hit: same result, bit for bit) instead of
-// costing a node fetch + a full node step that finds all four children behind the hit.  Entries are 8 bytes then (one
+// costing a node fetch + a full node step that finds all four children behind the hit.  Entries are 8 bytes (one
 // ds_write_b64 / ds_read_b64, conflict-free in the [entry][thread] layout), so a kernel keeps LSTK * 2 KiB of LDS per block.
-template <bool CULL> struct StackEntry { typedef int type; };
-template <> struct StackEntry<true> { typedef int2 type; };
 
 // trace_core is the traversal; trace_closest (one ray per lane, run to completion), trace_stream (lanes take their NEXT ray while the others
 // are still under way: compaction by refill, see there) and trace_occluded (any hit inside a segment, see there) are its three drivers.
@@ -369,16 +323,15 @@ template <> struct StackEntry<true> { typedef int2 type; };
 // its stack at the end of that leaf: the pop that ends the leaf finds nothing and the lane is finished, nothing is drained.  The accept test is the one
 // expression of the closest-hit form: a triangle's t and its inside test do not depend on h.t.
 struct NoNext { };
-template <bool STATS, int LSTK, int WIDTH, bool CULL, bool STREAM, bool ANY, typename Next>
+template <bool STATS, int LSTK, int WIDTH, bool STREAM, bool ANY, typename Next>
 __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy, float oz, float dx, float dy, float dz,
                                           uint32_t& n_nodes, uint32_t& n_tris, uint32_t* wave_iters, int refill_at, Next&& next, float t_start, float t_near)
 {
     static_assert(!(ANY && STREAM), "the any-hit form runs one ray per lane to completion");
-    typedef typename StackEntry<CULL>::type Entry;
+    typedef int2 Entry;                  // (child code, the child's entry distance)
     // what the traversal keeps of a ray (set by begin_ray; a streamed lane overwrites them when it takes its next ray)
     float idx, idy, idz, oodx, oody, oodz;
     uint32_t lon;
-#if TEXIR_TRI_WATERTIGHT
     // The ray-space shear of the watertight test: kz = dominant axis of the direction, (k1, k2) = the two axes that follow it cyclically;
     // a vertex A (relative to the origin) maps to x' = A[k1] - Sx A[kz], y' = A[k2] - Sy A[kz], z' = Sz A[kz], which sends d to (0, 0, 1).
     // (Woop et al. swap k1 / k2 for d[kz] < 0 to keep the winding: that negates U, V, W and their sum EXACTLY and changes neither the accept test --
@@ -387,7 +340,6 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
     // |dx| = |dy|-like plane) the leaf step runs a body specialised for that axis -- 3 sub + 2 fma + 1 mul per vertex, no component selects; the
     // per-lane body selects the components and then evaluates the SAME expressions, so a ray's hit does not depend on its wave's company.
     int kz; float Sx, Sy, Sz;
-#endif
     auto begin_ray = [&]() __attribute__((always_inline)) {
         const float ooeps = 8.271806e-25f;  // 2^-80
         idx = __builtin_amdgcn_rcpf(fabsf(dx) > ooeps ? dx : copysignf(ooeps, dx));
@@ -396,25 +348,17 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
         oodx = ox * idx; oody = oy * idy; oodz = oz * idz;
         // the ray's octant (bit a: negative direction along axis a), wave-uniform when the rays' signs agree: it names the body of a wave-uniform node step
         lon = (idx < 0.f ? 1u : 0u) | (idy < 0.f ? 2u : 0u) | (idz < 0.f ? 4u : 0u);
-#if TEXIR_TRI_WATERTIGHT
         const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
         kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
         const float dkz = kz == 0 ? dx : (kz == 1 ? dy : dz);
         const float dk1 = kz == 0 ? dy : (kz == 1 ? dz : dx), dk2 = kz == 0 ? dz : (kz == 1 ? dx : dy);
         Sz = __builtin_amdgcn_rcpf(dkz); Sx = dk1 * Sz; Sy = dk2 * Sz;
-#endif
     };
     if constexpr (!STREAM) begin_ray();
-    else { idx = idy = idz = oodx = oody = oodz = 0.f; lon = 0u;
-#if TEXIR_TRI_WATERTIGHT
-           kz = 0; Sx = Sy = Sz = 0.f;
-#endif
-    }
+    else { idx = idy = idz = oodx = oody = oodz = 0.f; lon = 0u; kz = 0; Sx = Sy = Sz = 0.f; }
     // what the lanes of the wave agree on (decided per ray batch; a streamed wave decides again after every refill, over the lanes that hold a ray)
     uint32_t son; bool signs_uniform;
-#if TEXIR_TRI_WATERTIGHT
-    int kz0; [[maybe_unused]] bool kz_uniform;
-#endif
+    int kz0; bool kz_uniform;
     // (`has`: this lane holds a ray under way -- always, except in a streamed wave)
     auto agree = [&](bool has) __attribute__((always_inline)) {
         if constexpr (STREAM) {
@@ -422,17 +366,13 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             const int src = m ? __ffsll((long long)m) - 1 : 0;
             son = (uint32_t)__builtin_amdgcn_readlane((int)lon, src);
             signs_uniform = WIDTH == 4 && sc.nodes4f != nullptr && !__any(has && lon != son);
-#if TEXIR_TRI_WATERTIGHT
             kz0 = __builtin_amdgcn_readlane(kz, src);
             kz_uniform = !__any(has && kz != kz0);
-#endif
         } else {
             son = (uint32_t)__builtin_amdgcn_readfirstlane((int)lon);
             signs_uniform = WIDTH == 4 && sc.nodes4f != nullptr && !__any(lon != son);
-#if TEXIR_TRI_WATERTIGHT
             kz0 = __builtin_amdgcn_readfirstlane(kz);
             kz_uniform = !__any(kz != kz0);
-#endif
         }
     };
     agree(true);
@@ -448,7 +388,7 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
     Entry* const base = lds_all + threadIdx.x;
     Entry* const lim = base + LSTK * kBlock;
     Entry* top = base;
-    auto make = [](int code, float tn) -> Entry { if constexpr (CULL) return make_int2(code, __float_as_int(tn)); else return code; };
+    auto make = [](int code, float tn) -> Entry { return make_int2(code, __float_as_int(tn)); };
     // (STATS, per lane: entries dropped by culling; pushes and pops that went through the private overflow array)
     auto count_culled = [&](uint32_t n) __attribute__((always_inline)) { if constexpr (STATS) { if (wave_iters) wave_iters[kWiCulled] += n; } };
     auto count_ovf = [&]() __attribute__((always_inline)) { if constexpr (STATS) { if (wave_iters && top >= lim) wave_iters[kWiOverflow]++; } };
@@ -468,8 +408,8 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             Entry v = *(top < lim ? top : lim - kBlock);
             if (__any(top >= lim)) { Entry b = ovf[top >= lim ? (top - lim) / kBlock : 0]; v = top >= lim ? b : v; }
             count_ovf();
-            if constexpr (CULL) { if (__int_as_float(v.y) < h.t) return v.x; count_culled(1u); }      // else: behind the closest hit, drop it
-            else return v;
+            if (__int_as_float(v.y) < h.t) return v.x;
+            count_culled(1u);                                  // behind the closest hit, drop it
         }
     };
     // The culling pop with every entry of the lane in LDS (the caller's wave-uniform guard).  Once a ray has found its hit most of its stack is dead, and the
@@ -478,42 +418,31 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
     // first, as a loop over single entries would -- the same entries are dropped and the same one is visited.  With one entry left the pair is (slot 0,
     // slot 1) and slot 1 -- free space inside the lane's column, never an address below `base` -- is ignored.
     auto pop_lds = [&]() __attribute__((always_inline)) -> int {
-        static_assert(!CULL || LSTK >= 2, "the paired read needs two LDS slots per lane");
-        if constexpr (CULL) {
-            // (the read is issued for every lane, from slot 0 where the stack is empty, instead of inside an exec-mask region of its own; the wave-uniform test
-            // repeats the callers' guard -- with it irt_group_kernel keeps its 800 bytes of scratch per lane, without it the register allocator takes 816)
-            Entry e0 = Entry();
-            if (!__any(top > lim)) e0 = *(top == base ? base : top - kBlock);
-            if (top == base) return kSentinel;
-            top -= kBlock;
-            if (__int_as_float(e0.y) < h.t) return e0.x;
-            count_culled(1u);
-            int n = kSentinel;
-#if TEXIR_STACK_DRAIN2
-            // (one exit, selects inside: the two loads are issued together and unconditionally -- the empty asm keeps the compiler from splitting them into
-            // a distance read, a branch and a code read per entry)
-            bool more = top != base;
-            while (more) {
-                const bool two = top != base + kBlock;
-                Entry* const lo = two ? top - 2 * kBlock : base;
-                Entry el = lo[0], eu = lo[kBlock];
-                asm volatile("" : "+v"(el.x), "+v"(el.y), "+v"(eu.x), "+v"(eu.y));
-                const bool au = two & (__int_as_float(eu.y) < h.t), al = __int_as_float(el.y) < h.t;
-                count_culled(au ? 0u : (two ? 1u : 0u) + (al ? 0u : 1u));
-                top = au ? top - kBlock : lo;
-                n = au ? eu.x : (al ? el.x : n);
-                more = !(au | al) & (top != base);
-            }
-#else
-            while (top != base) {
-                top -= kBlock;
-                const Entry e = *top;
-                if (__int_as_float(e.y) < h.t) { n = e.x; break; }
-                count_culled(1u);
-            }
-#endif
-            return n;
-        } else return kSentinel;
+        static_assert(LSTK >= 2, "the paired read needs two LDS slots per lane");
+        // (the read is issued for every lane, from slot 0 where the stack is empty, instead of inside an exec-mask region of its own; the wave-uniform test
+        // repeats the callers' guard -- with it irt_group_kernel keeps its 800 bytes of scratch per lane, without it the register allocator takes 816)
+        Entry e0 = Entry();
+        if (!__any(top > lim)) e0 = *(top == base ? base : top - kBlock);
+        if (top == base) return kSentinel;
+        top -= kBlock;
+        if (__int_as_float(e0.y) < h.t) return e0.x;
+        count_culled(1u);
+        int n = kSentinel;
+        // (one exit, selects inside: the two loads are issued together and unconditionally -- the empty asm keeps the compiler from splitting them into
+        // a distance read, a branch and a code read per entry)
+        bool more = top != base;
+        while (more) {
+            const bool two = top != base + kBlock;
+            Entry* const lo = two ? top - 2 * kBlock : base;
+            Entry el = lo[0], eu = lo[kBlock];
+            asm volatile("" : "+v"(el.x), "+v"(el.y), "+v"(eu.x), "+v"(eu.y));
+            const bool au = two & (__int_as_float(eu.y) < h.t), al = __int_as_float(el.y) < h.t;
+            count_culled(au ? 0u : (two ? 1u : 0u) + (al ? 0u : 1u));
+            top = au ? top - kBlock : lo;
+            n = au ? eu.x : (al ? el.x : n);
+            more = !(au | al) & (top != base);
+        }
+        return n;
     };
 
 #if TEXIR_CHAIN_PROBE
@@ -613,11 +542,7 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             if (key[2] < inf) { *top = make(code[2], key[2]); top += kBlock; }
             if (key[1] < inf) { *top = make(code[1], key[1]); top += kBlock; }
             if (key[0] < inf) node = code[0];
-            else if constexpr (CULL) {
-                node = pop_lds();
-            }
-            else if (top != base) { top -= kBlock; node = *reinterpret_cast<const int*>(top); }
-            else node = kSentinel;
+            else node = pop_lds();
         } else {
             if (key[3] < inf) push(code[3], key[3]);
             if (key[2] < inf) push(code[2], key[2]);
@@ -658,10 +583,9 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
         const uint32_t code = ~(uint32_t)node;
         // the pop that ends the leaf: the two-per-round-trip form unless some lane's stack reaches into the private overflow part (wave-uniform test)
         auto leaf_pop = [&]() __attribute__((always_inline)) -> int {
-            if constexpr (CULL) { if (!__any(top > lim)) return pop_lds(); }
+            if (!__any(top > lim)) return pop_lds();
             return pop();
         };
-#if TEXIR_QUAD
         if constexpr (WIDTH == 4) {
             // Quad records (bvh_build.h): three 16-byte words hold the four vertices of two triangles that share the edge (q1, q2): triangle 0 = (q0, q1, q2),
             // triangle 1 = (q3, q2, q1).  Four vertices are sheared instead of six, five edge functions evaluated instead of six -- the shared edge's value
@@ -702,13 +626,12 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             node = leaf_pop();
             return;
         }
-#endif
+        // the binary tree's leaves name triangle slots
         const int first = (int)(code >> 3), cnt = (int)(code & 7u) + 1;
         for (int i = first; i < first + cnt; i++) {
             const float4* tp = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(sc.tris) + (uint32_t)i * (uint32_t)(16 * kTriQuads));
             float4 v0 = tp[0], e1 = tp[1], e2 = tp[2];
             if (STATS) { n_tris++; if (wave_iters && first_active()) wave_iters[1]++; }
-#if TEXIR_TRI_WATERTIGHT
             // (tp[1], tp[2] hold the vertices v1, v2 here, not edges.)  Shear the three vertices into ray space ...
             auto shear = [&](float p0, float p1, float p2, float& X, float& Y, float& Z) __attribute__((always_inline)) {
                 const float q0 = p0 - ox, q1 = p1 - oy, q2 = p2 - oz;
@@ -730,32 +653,17 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             const float u = V * inv, v = W * inv;
             // inside <=> no two of the signs differ (zeros -- the origin exactly on an edge or vertex -- count as inside for BOTH neighbours)
             const bool ok = !((mn < 0.f) & (mxw > 0.f)) & (det != 0.f) & (t > t_accept) & (t < h.t);
-#else
-            // Moeller-Trumbore, same operation order as the oracle
-            float px = dy * e2.z - dz * e2.y, py = dz * e2.x - dx * e2.z, pz = dx * e2.y - dy * e2.x;
-            float det = e1.x * px + e1.y * py + e1.z * pz;
-            float inv = __builtin_amdgcn_rcpf(det);
-            float tx = ox - v0.x, ty = oy - v0.y, tz = oz - v0.z;
-            float u = (tx * px + ty * py + tz * pz) * inv;
-            float qx = ty * e1.z - tz * e1.y, qy = tz * e1.x - tx * e1.z, qz = tx * e1.y - ty * e1.x;
-            float v = (dx * qx + dy * qy + dz * qz) * inv;
-            float t = (e2.x * qx + e2.y * qy + e2.z * qz) * inv;
-            bool ok = (det != 0.f) & (u >= 0.f) & (u <= 1.f) & (v >= 0.f) & (u + v <= 1.f) & (t > t_accept) & (t < h.t);
-#endif
             if (ok) { h.t = t; h.u = u; h.v = v; h.slot = i; }
         }
         if constexpr (ANY) { if (h.slot >= 0) top = base; }
         node = leaf_pop();
     };
     auto leaf_step = [&]() __attribute__((always_inline)) {
-#if TEXIR_TRI_WATERTIGHT && TEXIR_LEAF_UNIFORM_KZ
         if (kz_uniform) {
             if (kz0 == 0) leaf_body(std::integral_constant<int, 0>{});
             else if (kz0 == 1) leaf_body(std::integral_constant<int, 1>{});
             else leaf_body(std::integral_constant<int, 2>{});
-        } else
-#endif
-        leaf_body(std::integral_constant<int, -1>{});
+        } else leaf_body(std::integral_constant<int, -1>{});
     };
     auto node_step = [&]() __attribute__((always_inline)) { if constexpr (WIDTH == 4) node_step4(); else node_step2(); };
 
@@ -790,7 +698,6 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
         }
         return h;
     } else {
-#if TEXIR_SCHED
     for (;;) {
         const bool at_node = (uint32_t)node < (uint32_t)kSentinel;        // an inner node (>= 0 and not the sentinel)
         const unsigned long long m_node = __ballot(at_node), m_leaf = __ballot(node < 0);
@@ -825,12 +732,6 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
         for (int q = 0; q < kProbeSlots; q++) probe_add(wave_iters[2 + q], v[q]);
     }
 #endif
-#else
-    while (node != kSentinel) {
-        while (node >= 0 && node != kSentinel) node_step();
-        while (node < 0) leaf_step();
-    }
-#endif
     return h;
     }
 }
@@ -838,35 +739,35 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
 // closest hit of one ray per lane, run to completion (all lanes of the wave enter and leave together).  One instance per kernel: it
 // owns the LDS part of the stacks.  STATS: n_nodes / n_tris count this lane's node fetches and triangle tests; wave_iters[0/1] (if
 // given) count, on the first active lane, how many times the wave executed the node-step and the triangle-test bodies.
-template <bool STATS, int LSTK = kLdsStack, int WIDTH = 2, bool CULL = false>
+template <bool STATS, int LSTK = kLdsStack, int WIDTH = 2>
 __device__ __forceinline__ Hit trace_closest(const SceneDev& sc, float ox, float oy, float oz, float dx, float dy, float dz,
                                              uint32_t& n_nodes, uint32_t& n_tris, uint32_t* wave_iters = nullptr)
 {
-    return trace_core<STATS, LSTK, WIDTH, CULL, false, false>(sc, ox, oy, oz, dx, dy, dz, n_nodes, n_tris, wave_iters, 64, NoNext{}, __builtin_inff(), 0.f);
+    return trace_core<STATS, LSTK, WIDTH, false, false>(sc, ox, oy, oz, dx, dy, dz, n_nodes, n_tris, wave_iters, 64, NoNext{}, __builtin_inff(), 0.f);
 }
 
 // Streamed form: every ray of the lane, the first one included, comes from `next`, which is called for the idle lanes once `refill_at` of them have
 // gathered (or the wave has run dry): next(finished, hit, dx, dy, dz) first consumes the finished ray's hit (finished = false on a lane's first call),
 // then returns true with the lane's next direction, or false when the lane has no ray left.
-template <bool STATS, int LSTK, int WIDTH, bool CULL, typename Next>
+template <bool STATS, int LSTK, int WIDTH, typename Next>
 __device__ __forceinline__ void trace_stream(const SceneDev& sc, float ox, float oy, float oz, uint32_t& n_nodes, uint32_t& n_tris, uint32_t* wave_iters,
                                              int refill_at, Next&& next)
 {
-    (void)trace_core<STATS, LSTK, WIDTH, CULL, true, false>(sc, ox, oy, oz, 0.f, 0.f, 0.f, n_nodes, n_tris, wave_iters, refill_at, next, __builtin_inff(), 0.f);
+    (void)trace_core<STATS, LSTK, WIDTH, true, false>(sc, ox, oy, oz, 0.f, 0.f, 0.f, n_nodes, n_tris, wave_iters, refill_at, next, __builtin_inff(), 0.f);
 }
 
 // Any hit inside a segment, one ray per lane, run to completion: true iff some triangle passes the leaf test above with t_near < t < t_far, t the float32 t
 // that test computes (include/texir_hip.h, texir_trace_occluded, states the rule).  At t_near = 0 this is the answer of `trace_closest(...).t < t_far`, bit for
-// bit: a box's computed entry distance is never above the computed t of a triangle inside it (what CULL already relies on), so a walk that starts with
+// bit: a box's computed entry distance is never above the computed t of a triangle inside it (what the culling pops already rely on), so a walk that starts with
 // h.t = t_far never culls a box that holds an accepted triangle with t < t_far, and "the closest accepted t is below t_far" says the same as "an accepted
 // triangle with t < t_far exists".  A lane stops at the end of the first leaf that accepts a triangle; a segment without one walks the boxes it crosses up
 // to t_far, in no particular need of their order.  t_far = NaN or <= t_near accepts nothing; a zero or non-finite direction accepts nothing (as closest hit).
 // One instance per kernel, like trace_closest: it owns the LDS part of the stacks.
-template <int LSTK, int WIDTH, bool CULL>
+template <int LSTK, int WIDTH>
 __device__ __forceinline__ bool trace_occluded(const SceneDev& sc, float ox, float oy, float oz, float dx, float dy, float dz, float t_near, float t_far)
 {
     uint32_t cn = 0, ct = 0;
-    return trace_core<false, LSTK, WIDTH, CULL, false, true>(sc, ox, oy, oz, dx, dy, dz, cn, ct, nullptr, 64, NoNext{}, t_far, t_near).slot >= 0;
+    return trace_core<false, LSTK, WIDTH, false, true>(sc, ox, oy, oz, dx, dy, dz, cn, ct, nullptr, 64, NoNext{}, t_far, t_near).slot >= 0;
 }
 
 __device__ __forceinline__ float wave_sum(float x)
@@ -913,14 +814,14 @@ __device__ __forceinline__ uint32_t cell_to_pass_m(uint32_t J, float sh0, float 
     return (th << bphi) | low;
 }
 
-// The direction cell J of the Lc-th cell a texel's passes walk; bphi / bth = the azimuth / elevation bits of the cell index.  TEXIR_PART_WEDGE = 1: the
+// The direction cell J of the Lc-th cell a texel's passes walk; bphi / bth = the azimuth / elevation bits of the cell index.  The
 // cells are walked azimuth-major (all elevations of one azimuth bin, then the next bin), so a part -- a contiguous range of Lc -- is an azimuthal WEDGE of
 // the hemisphere (N = 2048: 2 of the 64 azimuth bins = 5.6 degrees, all 32 elevations) instead of a full ring of one elevation.  The rays of a wedge leave
 // a surface patch towards one side of the room: what they touch deep in the tree, their triangles and their radiance-texture lines are shared by the
 // chunks of neighbouring wedges.  (irt_stream_kernel's `next` keeps this expression as text: see there.)
 __device__ __forceinline__ int wedge_cell(int Lc, int bphi, int bth)
 {
-    return TEXIR_PART_WEDGE ? (((Lc & ((1 << bth) - 1)) << bphi) | (Lc >> bth)) : Lc;
+    return ((Lc & ((1 << bth) - 1)) << bphi) | (Lc >> bth);
 }
 
 }  // namespace texir

@@ -7,8 +7,8 @@
 // coherent a ray bundle as the traversal gets.  A work item is (64-texel group, light); items are dealt statically: wave w of the grid takes items w,
 // w + waves, ... -- no work counter, no wave waits on another, every loop is bounded by K, S, the item count or the traversal's own bounds.  The light record
 // is a wave-uniform (scalar) load; the sample loop runs over i for the whole wave; a sample no lane of the wave needs is skipped by ballot.  Visibility is ONE
-// closest-hit query (device_common.h trace_closest<false, kLstk, WIDTH, kCull>, the single-ray kernels' shared form): occluded iff the closest hit has t < t_max.
-// ANY (texir_irt_lights_any): the same question put to trace_occluded<kLstk, WIDTH, kCull>(..., 0, t_max), which stops at the first accepted triangle: the
+// closest-hit query (device_common.h trace_closest<false, kLstk, WIDTH>, the single-ray kernels' shared form): occluded iff the closest hit has t < t_max.
+// ANY (texir_irt_lights_any): the same question put to trace_occluded<kLstk, WIDTH>(..., 0, t_max), which stops at the first accepted triangle: the
 // same answer per ray (see there), hence the same F and the same counts, bit for bit.
 // F is a pure function of the inputs: one float32 accumulator per (texel, light) in ascending i, no atomics on results, no workspace.
 #include <hip/hip_runtime.h>
@@ -97,12 +97,12 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
                 if (need) {
                     it_traced++;
                     if constexpr (ANY) {
-                        if (!trace_occluded<kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, 0.f, t_max)) {
+                        if (!trace_occluded<kLstk, WIDTH>(sc, px, py, pz, dx, dy, dz, 0.f, t_max)) {
                             it_visible++;
                             acc += g;
                         }
                     } else {
-                        const Hit hit = trace_closest<false, kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
+                        const Hit hit = trace_closest<false, kLstk, WIDTH>(sc, px, py, pz, dx, dy, dz, cn, ct);
                         if (!(hit.slot >= 0 && hit.t < t_max)) {
                             it_visible++;
                             acc += g;

@@ -21,7 +21,7 @@
 
 namespace texir {
 
-// (the traversal's template arguments are irt_group_kernel's on the 4-wide tree: device_common.h kGroupLstk, kCull)
+// (the traversal's template arguments are irt_group_kernel's on the 4-wide tree: device_common.h kGroupLstk)
 constexpr int kSplitMaxClasses = 8;
 
 // waves per SIMD the kernel is compiled for: 3 accumulators per class on top of irt_group_kernel's 64 registers at 8 waves
@@ -112,9 +112,9 @@ __global__ __launch_bounds__(kBlock, SplitWaves<KMAX>::value) void irt_split_ker
                 float s0 = shift_wrap_clamp(ham0(i, (uint32_t)N), sh0);
                 float s1 = shift_wrap_clamp(ham1(i), sh1);
                 float d[3];
-                sample_dir<TEXIR_IRT_FAST_SINCOS != 0>(mode, s0, s1, 0.f, f, d);
+                sample_dir(mode, s0, s1, 0.f, f, d);
                 const float ndl = fminf(fmaxf(nx * d[0] + ny * d[1] + nz * d[2], 0.f), 1.f);       // :170, RAW normal
-                Hit h = trace_closest<false, kGroupLstk, 4, kCull>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, nullptr);
+                Hit h = trace_closest<false, kGroupLstk, 4>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, nullptr);
                 if (h.slot >= 0 && h.t > 1e-4f) {          // tracer_o3d_irt.py:248
                     const SplitTaps tp = split_footprint(sc, labels, h.slot, h.u, h.v);
 #pragma unroll

@@ -53,11 +53,7 @@ __device__ __forceinline__ void irt_probe_flush(unsigned long long* stats, int l
 #endif
 
 constexpr int kEstimatorCosine = 4;      // or-ed into the IrT kernels' `mode`: the cosine branch of diffuse_reflectance (mat_nvdiffrast.py:256-257)
-// (occupancy and stack sizes of the kernels below: device_common.h kGroupWaves, kGroupLstk, kLstk, kCull)
-// chunk hand-out of irt_group_kernel (see there): 0 = one counter, parts = elevation rings (round 2)
-#ifndef TEXIR_XCD_SCHED
-#define TEXIR_XCD_SCHED 1
-#endif
+// (occupancy and stack sizes of the kernels below: device_common.h kGroupWaves, kGroupLstk, kLstk)
 
 // One texel per wave: the 64 lanes trace 64 samples of the texel per pass (any N, binary or 4-wide tree).  Kept as the
 // form for short texel lists (a 1024-point NIrF batch), for binary-tree scenes, and TEXIR_IRT_TEXELS_PER_WAVE=1.
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_kernel(SceneDev sc, c
                 float s1 = shift_wrap_clamp(ham1(i), sh1);
                 float d[3];
                 sample_dir(mode, s0, s1, 0.f, f, d);
-                Hit h = trace_closest<STATS, kGroupLstk, WIDTH, kCull>(sc, px, py, pz, d[0], d[1], d[2], c_nodes, c_tris, STATS ? wi : nullptr);
+                Hit h = trace_closest<STATS, kGroupLstk, WIDTH>(sc, px, py, pz, d[0], d[1], d[2], c_nodes, c_tris, STATS ? wi : nullptr);
                 if (STATS) c_rays++;
                 if (h.slot >= 0 && h.t > 1e-4f) {          // tracer_o3d_irt.py:248
                     float L[3];
@@ -131,12 +127,12 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
     const int part_cells = n_cells >> log2parts;
     // Which cells a part holds: an azimuthal wedge of the hemisphere (device_common.h wedge_cell); the hand-out below keeps neighbouring wedges on one XCD.
     const int cell_bits = log2N < 0 ? 0 : log2N - LOG2M, bphi = (cell_bits + 1) >> 1, bth = cell_bits - bphi;
-    // XCD-aware hand-out (TEXIR_XCD_SCHED = 1): the 8 XCDs have private 4 MiB L2s; with ONE chunk counter consecutive chunks -- the 32 parts of the
+    // XCD-aware hand-out: the 8 XCDs have private 4 MiB L2s; with ONE chunk counter consecutive chunks -- the 32 parts of the
     // same 64 texels -- go to whichever waves ask next, so every L2 sees every direction of every region.  Here each XCD owns parts / 8
     // neighbouring wedges (a 45-degree sector at N = 2048) of ALL texel groups and pulls them from its own counter (its own 128-byte line: 8
     // heads also dequeue faster than one, MI355X_MICROARCH.md "dequeue"); an XCD whose sector has run dry steals from the next one's.  HW_REG_XCC_ID
     // is a speed hint only: any wave may execute any chunk, the partial sums are indexed by (part, texel).
-    const int n_own = (TEXIR_XCD_SCHED && log2parts >= 3) ? 8 : 1;
+    const int n_own = log2parts >= 3 ? 8 : 1;
     const int log2ppo = log2parts - (n_own == 8 ? 3 : 0);                        // parts per owner
     const int64_t n_groups = (n_ids + GRP - 1) / GRP;
     int owner = n_own == 8 ? (__builtin_amdgcn_s_getreg(6164 /* hwreg(HW_REG_XCC_ID, 0, 4) */) & 7) : 0;
@@ -183,15 +179,15 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
                 float s0 = shift_wrap_clamp(ham0(i, (uint32_t)N), sh0);
                 float s1 = shift_wrap_clamp(ham1(i), sh1);
                 float d[3];
-                sample_dir<TEXIR_IRT_FAST_SINCOS != 0>(mode, s0, s1, 0.f, f, d);
+                sample_dir(mode, s0, s1, 0.f, f, d);
                 const float ndl = cosw ? 1.f : fminf(fmaxf(nx * d[0] + ny * d[1] + nz * d[2], 0.f), 1.f);       // :170, RAW normal (before the trace: one live register instead of three)
 #if TEXIR_CHAIN_PROBE
                 uint32_t tr_c0 = 0, tr_c1 = 0;
                 if (pass_timed) tr_c0 = probe_clock();
-                Hit h = trace_closest<STATS, kGroupLstk, WIDTH, kCull>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, wi);
+                Hit h = trace_closest<STATS, kGroupLstk, WIDTH>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, wi);
                 if (pass_timed) { tr_c1 = probe_clock(); probe_add(pv[13], tr_c1 - tr_c0); probe_add(pv[12], 1u); }
 #else
-                Hit h = trace_closest<STATS, kGroupLstk, WIDTH, kCull>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, STATS ? wi : nullptr);
+                Hit h = trace_closest<STATS, kGroupLstk, WIDTH>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, STATS ? wi : nullptr);
 #endif
                 if (STATS) c_rays++;
                 if (h.slot >= 0 && h.t > 1e-4f) {          // tracer_o3d_irt.py:248
@@ -240,11 +236,8 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
 // irt_group_kernel with compaction by refill (device_common.h trace_core<STREAM>): same chunks, same hand-out, same per-lane sample order and
 // partial sums; a lane whose ray has ended takes its texel's next direction cell as soon as `refill_at` lanes of the wave are idle instead of
 // waiting for the slowest ray of the pass.  Launched when TEXIR_IRT_REFILL = 1..63 (A/B switch); power-of-two N only.
-#ifndef TEXIR_STREAM_WAVES
-#define TEXIR_STREAM_WAVES TEXIR_GROUP_WAVES          // waves per SIMD the stream kernel is compiled for (A/B: fewer waves = more registers, fewer spills)
-#endif
 template <bool STATS, int WIDTH>
-__global__ __launch_bounds__(kBlock, TEXIR_STREAM_WAVES) void irt_stream_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm,
+__global__ __launch_bounds__(kBlock, kGroupWaves) void irt_stream_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm,
                                                             const float* __restrict__ shift, const int32_t* __restrict__ ids, int64_t n_ids,
                                                             int N, int log2N, int mode, float* __restrict__ irr,
                                                             unsigned long long* __restrict__ stats, unsigned long long* __restrict__ work,
@@ -258,7 +251,7 @@ __global__ __launch_bounds__(kBlock, TEXIR_STREAM_WAVES) void irt_stream_kernel(
     mode &= 3;
     const int part_cells = n_cells >> log2parts;
     const int bphi = (log2N + 1) >> 1, bth = log2N - bphi;
-    const int n_own = (TEXIR_XCD_SCHED && log2parts >= 3) ? 8 : 1;
+    const int n_own = log2parts >= 3 ? 8 : 1;
     const int log2ppo = log2parts - (n_own == 8 ? 3 : 0);
     const int64_t n_groups = (n_ids + GRP - 1) / GRP;
     int owner = n_own == 8 ? (__builtin_amdgcn_s_getreg(6164 /* hwreg(HW_REG_XCC_ID, 0, 4) */) & 7) : 0;
@@ -303,7 +296,7 @@ __global__ __launch_bounds__(kBlock, TEXIR_STREAM_WAVES) void irt_stream_kernel(
                     if (STATS) c_hits++;
                 }
                 if (Lc >= Lend) return false;
-                const int J = TEXIR_PART_WEDGE ? (((Lc & ((1 << bth) - 1)) << bphi) | (Lc >> bth)) : Lc;      // device_common.h wedge_cell, as text: the call re-schedules this lambda
+                const int J = ((Lc & ((1 << bth) - 1)) << bphi) | (Lc >> bth);      // device_common.h wedge_cell, as text: the call re-schedules this lambda
                 Lc++;
                 Frame f;
                 for (int a = 0; a < 3; a++) { f.n[a] = keep[a]; f.U[a] = keep[3 + a]; f.V[a] = keep[6 + a]; }
@@ -312,13 +305,13 @@ __global__ __launch_bounds__(kBlock, TEXIR_STREAM_WAVES) void irt_stream_kernel(
                 const float s0 = shift_wrap_clamp(ham0(i, (uint32_t)N), rs0);
                 const float s1 = shift_wrap_clamp(ham1(i), rs1);
                 float d[3];
-                sample_dir<TEXIR_IRT_FAST_SINCOS != 0>(mode, s0, s1, 0.f, f, d);
+                sample_dir(mode, s0, s1, 0.f, f, d);
                 ndl = cosw ? 1.f : fminf(fmaxf(rnx * d[0] + rny * d[1] + rnz * d[2], 0.f), 1.f);       // :170, RAW normal
                 dx = d[0]; dy = d[1]; dz = d[2];
                 if (STATS) c_rays++;
                 return true;
             };
-            trace_stream<STATS, kGroupLstk, WIDTH, kCull>(sc, px, py, pz, cn, ct, STATS ? wi : nullptr, refill_at, next);
+            trace_stream<STATS, kGroupLstk, WIDTH>(sc, px, py, pz, cn, ct, STATS ? wi : nullptr, refill_at, next);
             float* o = partial + ((int64_t)part * n_ids + k) * 3;
             o[0] = acc0; o[1] = acc1; o[2] = acc2;
         }
@@ -463,7 +456,7 @@ __global__ __launch_bounds__(kBlock) void trace_shade_kernel(SceneDev sc, const 
     for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < R; r += (int64_t)gridDim.x * kBlock) {
         float ox = org[3 * r], oy = org[3 * r + 1], oz = org[3 * r + 2];
         float dx = dir[3 * r], dy = dir[3 * r + 1], dz = dir[3 * r + 2];
-        Hit h = trace_closest<false, kLstk, WIDTH, kCull>(sc, ox, oy, oz, dx, dy, dz, cn, ct);
+        Hit h = trace_closest<false, kLstk, WIDTH>(sc, ox, oy, oz, dx, dy, dz, cn, ct);
         float L[3] = {0.f, 0.f, 0.f};
         bool hit = h.slot >= 0 && h.t > t_min;
         if (hit) shade_hit(sc, h.slot, h.u, h.v, L);
@@ -563,24 +556,11 @@ __device__ __forceinline__ SpecSample spec_sample(const Frame& f, float nx, floa
 #pragma clang fp contract(fast)
 
 // lanes-per-pixel = S when S is a power of two <= 64 (several pixels per wave), else 64 with ceil(S/64) passes
-#ifndef TEXIR_SPEC_WAVES
-#define TEXIR_SPEC_WAVES 0
-#endif
-#ifndef TEXIR_SPEC_LSTK
-#define TEXIR_SPEC_LSTK (TEXIR_SPEC_WAVES >= 7 && TEXIR_CULL ? (TEXIR_SPEC_WAVES >= 8 ? 10 : 11) : kLstk)
-#endif
-constexpr int kSpecLstk = TEXIR_SPEC_LSTK;
 // DW (forward only): the sample weights' derivatives d w_i / d roughness -- which the dual-number chain yields next to the weights at no extra fetch, in a
 // kernel that waits on memory with two thirds of its issue slots free -- are written to dw_ws [P,S]; the backward is then spec_bwd_ws_kernel, a stream over
 // (Ls, dw, d rgb), instead of this kernel's BWD form recomputing the whole sample chain (38 us of the material step: round 4).
 template <bool BWD, int WIDTH, bool DW = false>
-__global__
-#if TEXIR_SPEC_WAVES
-__launch_bounds__(kBlock, TEXIR_SPEC_WAVES)
-#else
-__launch_bounds__(kBlock)
-#endif
-void spec_kernel(SceneDev sc, const float* __restrict__ normal, const float* __restrict__ albedo,
+__global__ __launch_bounds__(kBlock) void spec_kernel(SceneDev sc, const float* __restrict__ normal, const float* __restrict__ albedo,
                                                       const float* __restrict__ rough, const float* __restrict__ points,
                                                       const float* __restrict__ irr, const float* __restrict__ cam,
                                                       const float* __restrict__ shift, int64_t P, int S, int lpp,
@@ -632,7 +612,7 @@ void spec_kernel(SceneDev sc, const float* __restrict__ normal, const float* __r
                         const float* lp = Ls_ws + 3 * ((size_t)p * S + i);
                         L[0] = lp[0]; L[1] = lp[1]; L[2] = lp[2];
                     } else {
-                        Hit h = trace_closest<false, kSpecLstk, WIDTH, kCull>(sc, ox, oy, oz, ss.l[0], ss.l[1], ss.l[2], cn, ct);
+                        Hit h = trace_closest<false, kLstk, WIDTH>(sc, ox, oy, oz, ss.l[0], ss.l[1], ss.l[2], cn, ct);
                         if (h.slot >= 0 && h.t > 1e-4f) shade_hit(sc, h.slot, h.u, h.v, L);
                         if (Ls_ws) { float* lp = Ls_ws + 3 * ((size_t)p * S + i); lp[0] = L[0]; lp[1] = L[1]; lp[2] = L[2]; }
                     }

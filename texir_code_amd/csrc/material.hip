@@ -53,15 +53,13 @@ __global__ __launch_bounds__(kBlock) void gbuffer_kernel(SceneDev sc, GbufArgs g
         const float s2 = 2.f / (float)g.c;
         float dXx = s2 * fb.dx[0], dXy = s2 * fb.dx[1], dXz = s2 * fb.dx[2];
         float dYx = s2 * fb.dy[0], dYy = s2 * fb.dy[1], dYz = s2 * fb.dy[2];
-        Hit h = trace_closest<false, kLstk, WIDTH, kCull>(sc, ex, ey, ez, dx, dy, dz, cn, ct);
+        Hit h = trace_closest<false, kLstk, WIDTH>(sc, ex, ey, ez, dx, dy, dz, cn, ct);
         float o_pos[3] = {1.f, 0.f, 0.f}, o_n[3] = {1.f, 0.f, 0.f}, o_uv[2] = {0.f, 0.f}, o_da[4] = {0.f, 0.f, 0.f, 0.f};   // bg (mat_nvdiffrast.py:125)
         float m = 0.f; int32_t tri = 0;
         if (h.slot >= 0) {
             const float4* tp = sc.tris + kTriQuads * (size_t)h.slot;
             float4 v0 = tp[0], e1 = tp[1], e2 = tp[2];
-#if TEXIR_TRI_WATERTIGHT
             e1.x -= v0.x; e1.y -= v0.y; e1.z -= v0.z; e2.x -= v0.x; e2.y -= v0.y; e2.z -= v0.z;      // the record holds v1, v2
-#endif
             m = 1.f; tri = (int32_t)tri_prim(sc, h.slot) + 1;
             const float u = h.u, v = h.v, w = 1.f - u - v;
             o_pos[0] = v0.x + u * e1.x + v * e2.x; o_pos[1] = v0.y + u * e1.y + v * e2.y; o_pos[2] = v0.z + u * e1.z + v * e2.z;
@@ -892,36 +890,21 @@ constexpr int adam_vec_epb(int C) { return C == 3 ? 960 : (1024 / (2 * C)) * (2 
 // that no 2x2 texel block straddles two blocks), every thread one float4 of each row; the level-1 gradient segment and the updated
 // texels go through LDS so that the level-1 texels come out in the mip build's own summation order ((p00 + p01) + p10) + p11.
 // Needs W*C % 4 == 0 (16-byte aligned rows); launch_adam_tex falls back to adam_tex_kernel otherwise.  Identical bits.
-// A/B switch of the build (make EXTRA=-DTEXIR_ADAM_NT=n): non-temporal hint on the step's loads (1), stores (2) or both (3) of texels and moments
-#ifndef TEXIR_ADAM_NT
-#define TEXIR_ADAM_NT 3          // measured (profiles/r04/adam_batch_probe_s15.txt): 310 -> 283 us per launch over both 4k textures, 5.5 -> 6.0 TB/s; loads or stores alone: a third of it each
-#endif
-#ifndef TEXIR_ADAM_WAVES
-#define TEXIR_ADAM_WAVES 5       // 94 VGPRs, no scratch (unbounded: 116 = 4 waves; 6: 24 bytes of scratch).  Alone the launch takes the same time at 4 / 5 / 6; inside the step 5 was 10 us ahead of 4
-#endif
-#if TEXIR_ADAM_WAVES
-#define TEXIR_ADAM_BOUNDS __launch_bounds__(256, TEXIR_ADAM_WAVES)
-#else
-#define TEXIR_ADAM_BOUNDS __launch_bounds__(256)
-#endif
+// Waves per SIMD the step is compiled for: 94 VGPRs, no scratch (unbounded: 116 = 4 waves; 6: 24 bytes of scratch).  Alone the launch takes the same
+// time at 4 / 5 / 6; inside the step 5 was 10 us ahead of 4.
+constexpr int kAdamWaves = 5;
+// The step's loads and stores of texels and moments carry the non-temporal hint.  Measured (profiles/r04/adam_batch_probe_s15.txt): 310 -> 283 us per
+// launch over both 4k textures, 5.5 -> 6.0 TB/s; loads or stores alone: a third of it each.
 typedef float texir_vf4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 adam_ld4(const float* __restrict__ q)
 {
-#if TEXIR_ADAM_NT & 1
     const texir_vf4 t = __builtin_nontemporal_load(reinterpret_cast<const texir_vf4*>(q));
     return make_float4(t.x, t.y, t.z, t.w);
-#else
-    return *reinterpret_cast<const float4*>(q);
-#endif
 }
 __device__ __forceinline__ void adam_st4(float* __restrict__ q, float a, float b, float c, float d)
 {
-#if TEXIR_ADAM_NT & 2
     texir_vf4 t; t.x = a; t.y = b; t.z = c; t.w = d;
     __builtin_nontemporal_store(t, reinterpret_cast<texir_vf4*>(q));
-#else
-    *reinterpret_cast<float4*>(q) = make_float4(a, b, c, d);
-#endif
 }
 
 //   * g1_mask (nullable, only together with g2): the level-1 stack is a never-cleared buffer; its texels carry this step's values only where the view's tap
@@ -1015,7 +998,7 @@ __device__ __forceinline__ void adam_tex_vec_body(float* __restrict__ p, const f
 }
 
 template <int C>
-__global__ TEXIR_ADAM_BOUNDS void adam_tex_vec_kernel(float* __restrict__ p, const float* __restrict__ g, const uint32_t* __restrict__ l0_mask,
+__global__ __launch_bounds__(256, kAdamWaves) void adam_tex_vec_kernel(float* __restrict__ p, const float* __restrict__ g, const uint32_t* __restrict__ l0_mask,
                                                            const float* __restrict__ g1, const float* __restrict__ g2, float* __restrict__ m, float* __restrict__ v, float* __restrict__ mip1,
                                                            int H, int W, float beta1, float beta2, float eps, float step_size, float bc2_sqrt, float lo, float hi, const float* __restrict__ hyp)
 {
@@ -1178,7 +1161,7 @@ __global__ __launch_bounds__(256) void mip_pyr_fold_batch_kernel(FoldBatch b)
 // CSET: bit C-1 set for every channel count that occurs in the batch -- the other bodies are not compiled in (the kernel's register count is the largest of
 // its bodies': 92 VGPRs with all four, 64 with the albedo + roughness pair)
 template <int CSET>
-__global__ TEXIR_ADAM_BOUNDS void adam_tex_vec_batch_kernel(AdamTexBatch b)
+__global__ __launch_bounds__(256, kAdamWaves) void adam_tex_vec_batch_kernel(AdamTexBatch b)
 {
     __shared__ float g1s[512];
     __shared__ float ps[2 * 1024];

@@ -22,7 +22,7 @@ __global__ __launch_bounds__(kBlock) void trace_occluded_kernel(SceneDev sc, con
         if (segment) {
             const float ox = org[3 * r], oy = org[3 * r + 1], oz = org[3 * r + 2];
             const float dx = dir[3 * r], dy = dir[3 * r + 1], dz = dir[3 * r + 2];
-            occ = trace_occluded<kLstk, WIDTH, kCull>(sc, ox, oy, oz, dx, dy, dz, t_near, t_far);
+            occ = trace_occluded<kLstk, WIDTH>(sc, ox, oy, oz, dx, dy, dz, t_near, t_far);
         }
         occluded[r] = occ ? 1 : 0;
         n_occluded += occ ? 1u : 0u;

@@ -8,8 +8,8 @@
 // bundle the traversal gets).  The views are walked in ascending order by the whole wave; the view's matrix and position are wave-uniform (scalar) loads.
 // A lane traces a view only when it faces it, its pixel is valid and its score beats the lane's best so far (views come in ascending order, so a tie never
 // replaces an earlier view: the lowest id keeps it); a view no lane of the wave needs is skipped by ballot.  The segment test is ONE closest-hit query
-// (device_common.h trace_closest<false, kLstk, WIDTH, kCull>, the single-ray kernels' shared form) with org = pos, dir = camera - pos: the view is occluded iff the closest hit has t < 1.
-// ANY (texir_atlas_bake_any): the same question put to trace_occluded<kLstk, WIDTH, kCull>(..., 0, 1), which stops at the first accepted triangle: the same
+// (device_common.h trace_closest<false, kLstk, WIDTH>, the single-ray kernels' shared form) with org = pos, dir = camera - pos: the view is occluded iff the closest hit has t < 1.
+// ANY (texir_atlas_bake_any): the same question put to trace_occluded<kLstk, WIDTH>(..., 0, 1), which stops at the first accepted triangle: the same
 // answer per pair (see there), hence the same view, pix, rgb and counts, bit for bit.
 // The outcome per texel is a pure function of the inputs: no atomics on results, nothing depends on the list's order or the launch shape.
 #include <hip/hip_runtime.h>
@@ -85,9 +85,9 @@ __global__ __launch_bounds__(kBlock) void atlas_bake_kernel(SceneDev sc, const f
             if (need) {
                 n_traced++;
                 bool occluded;
-                if constexpr (ANY) occluded = trace_occluded<kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, 0.f, 1.f);
+                if constexpr (ANY) occluded = trace_occluded<kLstk, WIDTH>(sc, px, py, pz, dx, dy, dz, 0.f, 1.f);
                 else {
-                    const Hit hit = trace_closest<false, kLstk, WIDTH, kCull>(sc, px, py, pz, dx, dy, dz, cn, ct);
+                    const Hit hit = trace_closest<false, kLstk, WIDTH>(sc, px, py, pz, dx, dy, dz, cn, ct);
                     occluded = hit.slot >= 0 && hit.t < 1.f;
                 }
                 if (!occluded) {

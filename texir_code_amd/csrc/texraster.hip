@@ -239,11 +239,7 @@ __global__ __launch_bounds__(kRB) void raster_resolve_kernel(SceneDev sc, const 
         const float S = (e0 + e1) + e2;
         b1 = e1 / S; b2 = e2 / S;
         const float4 q0 = sc.tris[3 * (size_t)slot], q1 = sc.tris[3 * (size_t)slot + 1], q2 = sc.tris[3 * (size_t)slot + 2];
-#if TEXIR_TRI_WATERTIGHT
-        const float3 s0 = make_float3(q0.x, q0.y, q0.z), s1 = make_float3(q1.x, q1.y, q1.z), s2 = make_float3(q2.x, q2.y, q2.z);
-#else
-        const float3 s0 = make_float3(q0.x, q0.y, q0.z), s1 = make_float3(q0.x + q1.x, q0.y + q1.y, q0.z + q1.z), s2 = make_float3(q0.x + q2.x, q0.y + q2.y, q0.z + q2.z);
-#endif
+        const float3 s0 = make_float3(q0.x, q0.y, q0.z), s1 = make_float3(q1.x, q1.y, q1.z), s2 = make_float3(q2.x, q2.y, q2.z);      // the record holds v1, v2
         float3 p0, p1, p2;
         unrotate(rot, s0, s1, s2, p0, p1, p2);
         const float ax = p1.x - p0.x, ay = p1.y - p0.y, az = p1.z - p0.z, bx = p2.x - p0.x, by = p2.y - p0.y, bz = p2.z - p0.z;

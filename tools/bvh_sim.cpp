@@ -145,12 +145,9 @@ int main(int argc, char** argv)
                     for (int k = 0; k < 4; k++) if (key[k] < INFINITY) stk.push_back(code[k]);
                 } else {
                     uint32_t code = ~(uint32_t)node; int first = (int)(code >> 3), cnt = (int)(code & 7u) + 1;
-#if TEXIR_QUAD
                     first *= 2; cnt *= 2;          // the 4-wide leaves name quad records: record r = slots 2 r, 2 r + 1 (an empty slot holds a degenerate triangle)
-#endif
                     for (int i = first; i < first + cnt; i++) {
                         const GpuTri& tr = h.tris[i];
-#if TEXIR_TRI_WATERTIGHT
                         // Woop/Benthin/Wald: shear to ray space (per-ray vectors mx, my, mz), exact-sign 2D edge functions
                         float P[3][3];
                         const float* vv[3] = {tr.v0, tr.e1, tr.e2};
@@ -172,7 +169,6 @@ int main(int argc, char** argv)
                         float T_ = Uf * P[0][2] + Vf * P[1][2] + Wf * P[2][2], t = T_ / det;
                         bool ok = !(mn < 0.f && mx > 0.f) && det != 0.f && t > 0.f && t < ht;
                         if (ok) { ht = t; slot = i; }
-#endif
                     }
                 }
                 if (stk.empty()) node = kSent; else { node = stk.back(); stk.pop_back(); }
@@ -202,9 +198,7 @@ int main(int argc, char** argv)
             if (code == kSent) continue;
             if (code >= 0) { for (int k = 0; k < 4; k++) st.push_back({h.nodes4[code].c[k], id}); continue; }
             uint32_t lc = ~(uint32_t)code; int first = (int)(lc >> 3), cnt = (int)(lc & 7u) + 1;
-#if TEXIR_QUAD
             first *= 2; cnt *= 2;
-#endif
             for (int i = first; i < first + cnt && i < (int)slot_subtree.size(); i++) slot_subtree[i] = id;
         }
         printf("regroup: blocks of %d waves, key %d, %d treelets\n", regB, regKey, next_id);
@@ -326,9 +320,7 @@ int main(int argc, char** argv)
                             const bool from_p = r.pleaf != 0;
                             uint32_t code = ~(uint32_t)(from_p ? r.pleaf : r.node);
                             int first = (int)(code >> 3), cnt = (int)(code & 7u) + 1;
-#if TEXIR_QUAD
                             first *= 2; cnt *= 2;  // (quad records, as above: the replay still counts per-triangle tests -- the kernel's leaf step covers a record's two at once)
-#endif
                             if (cnt > mx) mx = cnt;
                             pass_leaves.push_back((int)code);
                             for (int i = first; i < first + cnt; i++) {
