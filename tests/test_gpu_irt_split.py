@@ -1,4 +1,4 @@
-"""irt_split_kernel / irt_split_combine_kernel (csrc/irtsplit.hip) behind texir_irt_split, Scene.irt_split, the IrT stage's train.irt_split and the
+"""irt_split_kernel (csrc/irtsplit.hip) and irt_combine_kernel (csrc/kernels.hip) behind texir_irt_split, Scene.irt_split, the IrT stage's train.irt_split and the
 relight-irt command, on the golden room (20 k triangles, 256^2 texture, a lamp).
 
   1. intervals   every class of `lamp` and `bands` inside the float64 reference of its masked texture (irt_split_cases.split_ref);

@@ -113,6 +113,25 @@ __device__ __forceinline__ void sample_dir(int mode, float s0, float s1, float r
     for (int a = 0; a < 3; a++) L[a] = f.V[a] * sp + f.n[a] * ct + f.U[a] * cp;
 }
 
+// What the IrT kernels read of texel t: position, RAW normal, the two Cranley-Patterson shifts
+struct Texel { float px, py, pz, nx, ny, nz, sh0, sh1; };
+__device__ __forceinline__ Texel load_texel(const float* __restrict__ pos, const float* __restrict__ nrm, const float* __restrict__ shift, int64_t t)
+{
+    Texel x;
+    x.px = pos[3 * t]; x.py = pos[3 * t + 1]; x.pz = pos[3 * t + 2];
+    x.nx = nrm[3 * t]; x.ny = nrm[3 * t + 1]; x.nz = nrm[3 * t + 2];
+    x.sh0 = shift[2 * t]; x.sh1 = shift[2 * t + 1];
+    return x;
+}
+
+// direction of sample i of N of a texel with shifts (sh0, sh1) and frame f, as the IrT kernels take it (no roughness: modes 0, 1)
+__device__ __forceinline__ void texel_sample_dir(int mode, uint32_t i, uint32_t N, float sh0, float sh1, const Frame& f, float* d)
+{
+    const float s0 = shift_wrap_clamp(ham0(i, N), sh0);
+    const float s1 = shift_wrap_clamp(ham1(i), sh1);
+    sample_dir(mode, s0, s1, 0.f, f, d);
+}
+
 // corner uvs of the triangle in leaf slot `slot`: a = (uv0, uv1), b = (uv2, -, -)
 __device__ __forceinline__ void tri_uvs(const SceneDev& sc, int slot, float4& a, float4& b)
 {
@@ -784,6 +803,20 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x)
 
 // neither inf nor nan
 __device__ __forceinline__ bool finite32(float x) { return x - x == 0.f; }
+
+// The IrT estimator's scale of a summed texel: sum * 2 * np.pi / N (tracer_o3d_irt.py:171); `two` = 1 for the cosine estimator, sum * np.pi / N
+// (mat_nvdiffrast.py:256-257).  Three separately rounded operations, in this order, wherever a kernel finishes a texel.
+__device__ __forceinline__ float irt_scale(float acc, float two, int N) { return ((acc * two) * 3.141592653589793f) / (float)N; }
+
+// The wave's next ticket of a work counter: lane 0 takes it, every lane gets it (two readfirstlane: the ticket stays wave-uniform, in SGPRs).
+// Persistent waves pull chunks from a counter: a chunk is milliseconds of work, so a static round-robin would leave the slowest wave's surplus (the sum of
+// its chunk-time deviations) as an idle tail.
+__device__ __forceinline__ unsigned long long wave_take(unsigned long long* counter, int lane)
+{
+    unsigned long long x = 0;
+    if (lane == 0) x = atomicAdd(counter, 1ull);
+    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(x >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+}
 
 // ------------------------------------------------------------------------------------------------
 // sample order of the multi-texel IrT kernels (irt_group_kernel, irt_stream_kernel, irt_split_kernel).  A wave traces GRP neighbouring texels at

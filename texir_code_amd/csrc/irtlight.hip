@@ -40,12 +40,8 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
         int64_t tex = i < n ? (ids ? (int64_t)ids[i] : i) : -1;
         if (tex >= Nt) tex = -1;                                           // an id outside [0, Nt) is not a texel: nothing is read or written for it
         const bool live = tex >= 0;
-        float px = 0.f, py = 0.f, pz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f, sh0 = 0.f, sh1 = 0.f;
-        if (live) {
-            px = pos[3 * tex]; py = pos[3 * tex + 1]; pz = pos[3 * tex + 2];
-            nx = nrm[3 * tex]; ny = nrm[3 * tex + 1]; nz = nrm[3 * tex + 2];
-            sh0 = shift[2 * tex]; sh1 = shift[2 * tex + 1];
-        }
+        Texel x = {};
+        if (live) x = load_texel(pos, nrm, shift, tex);
         // the record: wave-uniform, scalar loads.  Device data the host never saw: everything is decided here.
         const float* L = lights + 16 * (size_t)k;
         const float kind = L[0];
@@ -69,8 +65,8 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
         uint32_t it_traced = 0, it_visible = 0;
         if (valid) {                                                        // (wave-uniform)
             for (int s = 0; s < S; s++) {
-                const float s0 = shift_wrap_clamp(ham0((uint32_t)s, (uint32_t)S), sh0);
-                const float s1 = shift_wrap_clamp(ham1((uint32_t)s), sh1);
+                const float s0 = shift_wrap_clamp(ham0((uint32_t)s, (uint32_t)S), x.sh0);
+                const float s1 = shift_wrap_clamp(ham1((uint32_t)s), x.sh1);
                 float yx, yy, yz;
                 if (quad) {
                     yx = (cx + s0 * ax) + s1 * bx;
@@ -83,9 +79,9 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
                     mx = q * cosf(phi); my = q * sinf(phi); mz = z;
                     yx = cx + ax * mx; yy = cy + ax * my; yz = cz + ax * mz;
                 }
-                const float dx = yx - px, dy = yy - py, dz = yz - pz;
+                const float dx = yx - x.px, dy = yy - x.py, dz = yz - x.pz;
                 const float dd = (dx * dx + dy * dy) + dz * dz;
-                const float nd = (nx * dx + ny * dy) + nz * dz;
+                const float nd = (x.nx * dx + x.ny * dy) + x.nz * dz;
                 const float md = -((mx * dx + my * dy) + mz * dz);
                 float g = 0.f;
                 if (live && nd > 0.f && md > 0.f && dd > 0.f) {
@@ -97,12 +93,12 @@ __global__ __launch_bounds__(kBlock) void irt_lights_kernel(SceneDev sc, const f
                 if (need) {
                     it_traced++;
                     if constexpr (ANY) {
-                        if (!trace_occluded<kLstk, WIDTH>(sc, px, py, pz, dx, dy, dz, 0.f, t_max)) {
+                        if (!trace_occluded<kLstk, WIDTH>(sc, x.px, x.py, x.pz, dx, dy, dz, 0.f, t_max)) {
                             it_visible++;
                             acc += g;
                         }
                     } else {
-                        const Hit hit = trace_closest<false, kLstk, WIDTH>(sc, px, py, pz, dx, dy, dz, cn, ct);
+                        const Hit hit = trace_closest<false, kLstk, WIDTH>(sc, x.px, x.py, x.pz, dx, dy, dz, cn, ct);
                         if (!(hit.slot >= 0 && hit.t < t_max)) {
                             it_visible++;
                             acc += g;

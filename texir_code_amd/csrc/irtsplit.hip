@@ -7,7 +7,7 @@
 //
 // A wave owns 64 consecutive ids of the caller's (Morton-ordered) list; a chunk is 64 texels x one part of the passes.  Chunks are dealt statically: wave w
 // of the grid takes chunks w, w + waves, ... -- no work counter, no wave waits on another, every loop is bounded by N, the chunk count or the traversal's
-// own bounds.  The partial sums go to partial[part][k][i][3] and irt_split_combine_kernel adds them in part order, so the result is a pure function of the
+// own bounds.  The partial sums go to partial[part][k][i][3] and irt_combine_kernel (kernels.hip) adds them in part order, so the result is a pure function of the
 // inputs: list order, list cuts, launch shape and stream do not change a bit.
 //
 // The class accumulators are registers under static indexing (loops over KMAX are unrolled, the class of a tap is applied by selects); the only private
@@ -97,10 +97,8 @@ __global__ __launch_bounds__(kBlock, SplitWaves<KMAX>::value) void irt_split_ker
         const int64_t k = (chunk >> log2parts) * 64 + lane;
         const bool live = k < n_ids;
         const int64_t t = live ? (ids ? (int64_t)ids[k] : k) : 0;
-        const float px = pos[3 * t], py = pos[3 * t + 1], pz = pos[3 * t + 2];
-        const float nx = nrm[3 * t], ny = nrm[3 * t + 1], nz = nrm[3 * t + 2];
-        const float sh0 = shift[2 * t], sh1 = shift[2 * t + 1];
-        const Frame f = make_frame(nx, ny, nz);
+        const Texel x = load_texel(pos, nrm, shift, t);
+        const Frame f = make_frame(x.nx, x.ny, x.nz);
         float acc[KMAX][3];
 #pragma unroll
         for (int q = 0; q < KMAX; q++) { acc[q][0] = 0.f; acc[q][1] = 0.f; acc[q][2] = 0.f; }
@@ -108,13 +106,11 @@ __global__ __launch_bounds__(kBlock, SplitWaves<KMAX>::value) void irt_split_ker
             const int J = log2N >= 0 ? wedge_cell(Lc, bphi, bth) : Lc;
             if (live) {
                 // (N not a power of two: natural sample order)
-                const uint32_t i = log2N < 0 ? (uint32_t)J : sample_index_m(cell_to_pass_m((uint32_t)J, sh0, sh1, log2N, 0), 0u, log2N, 0);
-                float s0 = shift_wrap_clamp(ham0(i, (uint32_t)N), sh0);
-                float s1 = shift_wrap_clamp(ham1(i), sh1);
+                const uint32_t i = log2N < 0 ? (uint32_t)J : sample_index_m(cell_to_pass_m((uint32_t)J, x.sh0, x.sh1, log2N, 0), 0u, log2N, 0);
                 float d[3];
-                sample_dir(mode, s0, s1, 0.f, f, d);
-                const float ndl = fminf(fmaxf(nx * d[0] + ny * d[1] + nz * d[2], 0.f), 1.f);       // :170, RAW normal
-                Hit h = trace_closest<false, kGroupLstk, 4>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, nullptr);
+                texel_sample_dir(mode, i, (uint32_t)N, x.sh0, x.sh1, f, d);
+                const float ndl = fminf(fmaxf(x.nx * d[0] + x.ny * d[1] + x.nz * d[2], 0.f), 1.f);       // :170, RAW normal
+                Hit h = trace_closest<false, kGroupLstk, 4>(sc, x.px, x.py, x.pz, d[0], d[1], d[2], cn, ct, nullptr);
                 if (h.slot >= 0 && h.t > 1e-4f) {          // tracer_o3d_irt.py:248
                     const SplitTaps tp = split_footprint(sc, labels, h.slot, h.u, h.v);
 #pragma unroll
@@ -142,23 +138,6 @@ __global__ __launch_bounds__(kBlock, SplitWaves<KMAX>::value) void irt_split_ker
     }
 }
 
-// out[k][t] = (2 pi / N) * (partial sums of the texel's parts, added in part order), as irt_combine_kernel writes it
-__global__ __launch_bounds__(256) void irt_split_combine_kernel(const float* __restrict__ partial, const int32_t* __restrict__ ids, int64_t n_ids, int64_t Nt, int K,
-                                                                int parts, int N, float two, float* __restrict__ out)
-{
-    const float pi = 3.141592653589793f;
-    const int64_t per_class = 3 * n_ids, total = per_class * K;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t q = e / per_class, r = e - q * per_class;
-        const int64_t k = r / 3;
-        const int c = (int)(r - 3 * k);
-        float a = partial[e];
-        for (int p = 1; p < parts; p++) a += partial[(int64_t)p * total + e];
-        const int64_t t = ids ? (int64_t)ids[k] : k;
-        out[(q * Nt + t) * 3 + c] = ((a * two) * pi) / (float)N;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // launcher
 // ------------------------------------------------------------------------------------------------
@@ -176,10 +155,7 @@ template <int KMAX, bool UNIT>
 static void split_launch(const SceneDev& sc, const float* tex, const uint8_t* labels, const float* pos, const float* nrm, const float* shift, const int32_t* ids,
                          int64_t n_ids, int N, int l2, int mode, int K, float* partial, int log2parts, hipStream_t st)
 {
-    const int64_t chunks = ((n_ids + 63) / 64) << log2parts;
-    const int64_t want = (chunks + (kBlock / 64) - 1) / (kBlock / 64);
-    int grid = resident_grid(irt_split_kernel<KMAX, UNIT>, kBlock);
-    if (want < grid) grid = (int)want;
+    const int grid = persistent_grid(irt_split_kernel<KMAX, UNIT>, ((n_ids + 63) / 64) << log2parts, kBlock);      // a wave per chunk, at most the resident ones
     hipLaunchKernelGGL((irt_split_kernel<KMAX, UNIT>), dim3(grid), dim3(kBlock), 0, st, sc, tex, labels, pos, nrm, shift, ids, n_ids, N, l2, mode, K, partial, log2parts);
 }
 
@@ -198,8 +174,7 @@ hipError_t launch_irt_split(const SceneDev& sc, const float* tex_row_major, cons
 #undef TEXIR_SPLIT
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(irt_split_combine_kernel, dim3(grid_capped(256, 3 * n_ids * K)), dim3(256), 0, st, partial, ids, n_ids, Nt, K, 1 << log2parts, N, 2.f, out);
-    return hipGetLastError();
+    return launch_irt_combine(partial, ids, n_ids, Nt, K, 1 << log2parts, N, 2.f, out, st);
 }
 
 }  // namespace texir

@@ -14,6 +14,8 @@ size_t irt_scratch_bytes(const SceneDev& sc, int64_t n_ids, int N);      // byte
 constexpr int kWorkStride = 16;              // unsigned long longs between the per-XCD chunk counters of one launch (a 128-byte line each)
 hipError_t irt_probe_node_utilisation(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids, int64_t first, int64_t count,
                                       int N, int mode, unsigned long long* work, hipStream_t st, double* util);
+// out[q][t] of K planes of Nt texels = irt_scale of the listed texels' part sums partial[part][q][k][3], added in part order (K = 1: Nt is not used)
+hipError_t launch_irt_combine(const float* partial, const int32_t* ids /*nullable*/, int64_t n_ids, int64_t Nt, int K, int parts, int N, float two, float* out, hipStream_t st);
 struct IrtPlan { int per_wave, log2parts, width; char name[64]; };
 IrtPlan irt_plan(const SceneDev& sc, int64_t n_ids, int N);      // the kernel form launch_irt picks for this call
 hipError_t launch_prefetch(const void* p, size_t bytes, int blocks, uint32_t* sink, hipStream_t st);

@@ -18,6 +18,8 @@ namespace texir {
 // samples a wave traces together fall into one (phi-bin, cos-theta-bin) cell of the Hammersley lattice
 // (i's low bits are phi's high bits after the radical inverse; i's high bits are theta).  Coherent rays share
 // the upper BVH levels => the wave's node fetches coalesce.
+// (From 128 samples up this is device_common.h sample_index_m(pass, lane, log2N, 6); written out because that function's guard for a cell index
+// without elevation bits costs irt_kernel a compare and a select per pass.)
 __device__ __forceinline__ uint32_t sample_index(uint32_t pass, uint32_t lane, uint32_t N, int log2N)
 {
     if (log2N < 7) return pass * 64u + lane;             // N not a power of two or N <= 64: natural order
@@ -71,25 +73,21 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_kernel(SceneDev sc, c
     const int passes = (N + 63) >> 6;
     for (int64_t k = gw; k < n_ids; k += nw) {
         const int64_t t = ids ? (int64_t)ids[k] : k;
-        const float px = pos[3 * t], py = pos[3 * t + 1], pz = pos[3 * t + 2];
-        const float nx = nrm[3 * t], ny = nrm[3 * t + 1], nz = nrm[3 * t + 2];
-        const float sh0 = shift[2 * t], sh1 = shift[2 * t + 1];
-        const Frame f = make_frame(nx, ny, nz);
+        const Texel x = load_texel(pos, nrm, shift, t);
+        const Frame f = make_frame(x.nx, x.ny, x.nz);
         float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
         for (int p = 0; p < passes; p++) {
             uint32_t i = sample_index((uint32_t)p, (uint32_t)lane, (uint32_t)N, log2N);
             if (i < (uint32_t)N) {
-                float s0 = shift_wrap_clamp(ham0(i, (uint32_t)N), sh0);
-                float s1 = shift_wrap_clamp(ham1(i), sh1);
                 float d[3];
-                sample_dir(mode, s0, s1, 0.f, f, d);
-                Hit h = trace_closest<STATS, kGroupLstk, WIDTH>(sc, px, py, pz, d[0], d[1], d[2], c_nodes, c_tris, STATS ? wi : nullptr);
+                texel_sample_dir(mode, i, (uint32_t)N, x.sh0, x.sh1, f, d);
+                Hit h = trace_closest<STATS, kGroupLstk, WIDTH>(sc, x.px, x.py, x.pz, d[0], d[1], d[2], c_nodes, c_tris, STATS ? wi : nullptr);
                 if (STATS) c_rays++;
                 if (h.slot >= 0 && h.t > 1e-4f) {          // tracer_o3d_irt.py:248
                     float L[3];
                     shade_hit(sc, h.slot, h.u, h.v, L);
                     // :170 clamp(n . l, 0, 1) with the RAW normal
-                    float ndl = cosw ? 1.f : fminf(fmaxf(nx * d[0] + ny * d[1] + nz * d[2], 0.f), 1.f);
+                    float ndl = cosw ? 1.f : fminf(fmaxf(x.nx * d[0] + x.ny * d[1] + x.nz * d[2], 0.f), 1.f);
                     acc0 += L[0] * ndl; acc1 += L[1] * ndl; acc2 += L[2] * ndl;
                     if (STATS) c_hits++;
                 }
@@ -97,11 +95,8 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_kernel(SceneDev sc, c
         }
         acc0 = wave_sum(acc0); acc1 = wave_sum(acc1); acc2 = wave_sum(acc2);
         if (lane == 0) {
-            // :171  sum * 2 * np.pi / N      (cosine estimator, mat_nvdiffrast.py:256-257: sum * np.pi / N)
-            const float pi = 3.141592653589793f, two = cosw ? 1.f : 2.f;
-            irr[3 * t] = ((acc0 * two) * pi) / (float)N;
-            irr[3 * t + 1] = ((acc1 * two) * pi) / (float)N;
-            irr[3 * t + 2] = ((acc2 * two) * pi) / (float)N;
+            const float two = cosw ? 1.f : 2.f;
+            irr[3 * t] = irt_scale(acc0, two, N); irr[3 * t + 1] = irt_scale(acc1, two, N); irr[3 * t + 2] = irt_scale(acc2, two, N);
         }
     }
     if (STATS) irt_stats_flush(stats, lane, c_rays, c_nodes, c_tris, c_hits, wi);
@@ -138,12 +133,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
     int owner = n_own == 8 ? (__builtin_amdgcn_s_getreg(6164 /* hwreg(HW_REG_XCC_ID, 0, 4) */) & 7) : 0;
     int dry = 0;
     for (;;) {
-        // persistent waves pull chunks from a counter: a chunk is milliseconds of work, so a static round-robin would
-        // leave the slowest wave's surplus (the sum of its chunk-time deviations) as an idle tail
-        unsigned long long chunk = 0;
-        if (lane == 0) chunk = atomicAdd(work + owner * kWorkStride, 1ull);
-        chunk = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(chunk >> 32)) << 32) |
-                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)chunk);
+        const unsigned long long chunk = wave_take(work + owner * kWorkStride, lane);
         if ((int64_t)(chunk >> log2ppo) >= n_groups) {
             if (++dry >= n_own) break;                                           // every owner's queue is empty
             owner = (owner + 1) & (n_own - 1);
@@ -160,6 +150,8 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
         const int64_t k = k0 + grp;
         const bool live = k < n_ids;
         const int64_t t = live ? (ids ? (int64_t)ids[k] : k) : 0;
+        // (load_texel as text: through the call, the TEXIR_CHAIN_PROBE build of this kernel -- the one profiles/chain_*.json describe -- places the stores of
+        // its tail differently, 16 instructions more)
         const float px = pos[3 * t], py = pos[3 * t + 1], pz = pos[3 * t + 2];
         const float nx = nrm[3 * t], ny = nrm[3 * t + 1], nz = nrm[3 * t + 2];
         const float sh0 = shift[2 * t], sh1 = shift[2 * t + 1];
@@ -176,10 +168,8 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
             if (live) {
                 // (N not a power of two: only the one-sample-per-pass form is launched, in natural sample order)
                 const uint32_t i = log2N < 0 ? (uint32_t)J : sample_index_m(cell_to_pass_m((uint32_t)J, sh0, sh1, log2N, LOG2M), (uint32_t)sub, log2N, LOG2M);
-                float s0 = shift_wrap_clamp(ham0(i, (uint32_t)N), sh0);
-                float s1 = shift_wrap_clamp(ham1(i), sh1);
                 float d[3];
-                sample_dir(mode, s0, s1, 0.f, f, d);
+                texel_sample_dir(mode, i, (uint32_t)N, sh0, sh1, f, d);
                 const float ndl = cosw ? 1.f : fminf(fmaxf(nx * d[0] + ny * d[1] + nz * d[2], 0.f), 1.f);       // :170, RAW normal (before the trace: one live register instead of three)
 #if TEXIR_CHAIN_PROBE
                 uint32_t tr_c0 = 0, tr_c1 = 0;
@@ -216,10 +206,8 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
                 float* o = partial + ((int64_t)part * n_ids + k) * 3;
                 o[0] = acc0; o[1] = acc1; o[2] = acc2;
             } else {
-                const float pi = 3.141592653589793f, two = cosw ? 1.f : 2.f;
-                irr[3 * t] = ((acc0 * two) * pi) / (float)N;
-                irr[3 * t + 1] = ((acc1 * two) * pi) / (float)N;
-                irr[3 * t + 2] = ((acc2 * two) * pi) / (float)N;
+                const float two = cosw ? 1.f : 2.f;
+                irr[3 * t] = irt_scale(acc0, two, N); irr[3 * t + 1] = irt_scale(acc1, two, N); irr[3 * t + 2] = irt_scale(acc2, two, N);
             }
         }
 #if TEXIR_CHAIN_PROBE
@@ -251,16 +239,15 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_stream_kernel(SceneDe
     mode &= 3;
     const int part_cells = n_cells >> log2parts;
     const int bphi = (log2N + 1) >> 1, bth = log2N - bphi;
+    // (the XCD-aware hand-out of irt_group_kernel, explained there; the loop is kept as text in both kernels: shared through helpers, as one queue object
+    // or as single-attempt functions, it costs each of the two shipped kernels 1 to 53 instructions)
     const int n_own = log2parts >= 3 ? 8 : 1;
     const int log2ppo = log2parts - (n_own == 8 ? 3 : 0);
     const int64_t n_groups = (n_ids + GRP - 1) / GRP;
     int owner = n_own == 8 ? (__builtin_amdgcn_s_getreg(6164 /* hwreg(HW_REG_XCC_ID, 0, 4) */) & 7) : 0;
     int dry = 0;
     for (;;) {
-        unsigned long long chunk = 0;
-        if (lane == 0) chunk = atomicAdd(work + owner * kWorkStride, 1ull);
-        chunk = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(chunk >> 32)) << 32) |
-                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)chunk);
+        const unsigned long long chunk = wave_take(work + owner * kWorkStride, lane);
         if ((int64_t)(chunk >> log2ppo) >= n_groups) {
             if (++dry >= n_own) break;
             owner = (owner + 1) & (n_own - 1);
@@ -271,9 +258,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_stream_kernel(SceneDe
         const int64_t k = (int64_t)(chunk >> log2ppo) * GRP + lane;
         const bool live = k < n_ids;
         const int64_t t = live ? (ids ? (int64_t)ids[k] : k) : 0;
-        const float px = pos[3 * t], py = pos[3 * t + 1], pz = pos[3 * t + 2];
-        const float nx = nrm[3 * t], ny = nrm[3 * t + 1], nz = nrm[3 * t + 2];
-        const float sh0 = shift[2 * t], sh1 = shift[2 * t + 1];
+        const Texel x = load_texel(pos, nrm, shift, t);
         float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
         if (live) {
             // What a refill needs of the texel (frame, raw normal, shifts: 14 floats) is PARKED in private memory for the whole chunk and read back only
@@ -281,9 +266,9 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_stream_kernel(SceneDe
             // spills in every node step, 4x slower than the lock-step kernel).  volatile = the compiler keeps the array in memory.
             volatile float keep[14];
             {
-                const Frame f = make_frame(nx, ny, nz);
+                const Frame f = make_frame(x.nx, x.ny, x.nz);
                 for (int a = 0; a < 3; a++) { keep[a] = f.n[a]; keep[3 + a] = f.U[a]; keep[6 + a] = f.V[a]; }
-                keep[9] = nx; keep[10] = ny; keep[11] = nz; keep[12] = sh0; keep[13] = sh1;
+                keep[9] = x.nx; keep[10] = x.ny; keep[11] = x.nz; keep[12] = x.sh0; keep[13] = x.sh1;
             }
             int Lc = part * part_cells;
             const int Lend = Lc + part_cells;
@@ -302,16 +287,14 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_stream_kernel(SceneDe
                 for (int a = 0; a < 3; a++) { f.n[a] = keep[a]; f.U[a] = keep[3 + a]; f.V[a] = keep[6 + a]; }
                 const float rnx = keep[9], rny = keep[10], rnz = keep[11], rs0 = keep[12], rs1 = keep[13];
                 const uint32_t i = sample_index_m(cell_to_pass_m((uint32_t)J, rs0, rs1, log2N, 0), 0u, log2N, 0);
-                const float s0 = shift_wrap_clamp(ham0(i, (uint32_t)N), rs0);
-                const float s1 = shift_wrap_clamp(ham1(i), rs1);
                 float d[3];
-                sample_dir(mode, s0, s1, 0.f, f, d);
+                texel_sample_dir(mode, i, (uint32_t)N, rs0, rs1, f, d);
                 ndl = cosw ? 1.f : fminf(fmaxf(rnx * d[0] + rny * d[1] + rnz * d[2], 0.f), 1.f);       // :170, RAW normal
                 dx = d[0]; dy = d[1]; dz = d[2];
                 if (STATS) c_rays++;
                 return true;
             };
-            trace_stream<STATS, kGroupLstk, WIDTH>(sc, px, py, pz, cn, ct, STATS ? wi : nullptr, refill_at, next);
+            trace_stream<STATS, kGroupLstk, WIDTH>(sc, x.px, x.py, x.pz, cn, ct, STATS ? wi : nullptr, refill_at, next);
             float* o = partial + ((int64_t)part * n_ids + k) * 3;
             o[0] = acc0; o[1] = acc1; o[2] = acc2;
         }
@@ -324,19 +307,27 @@ __global__ __launch_bounds__(128) void clear_u64_kernel(unsigned long long* __re
     for (int i = threadIdx.x; i < n; i += 128) p[i] = 0ull;
 }
 
-// irr[t] = (2 pi / N) * (partial sums of the texel's pass ranges, added in part order)          (tracer_o3d_irt.py:171)
-__global__ __launch_bounds__(256) void irt_combine_kernel(const float* __restrict__ partial, const int32_t* __restrict__ ids, int64_t n_ids,
-                                                          int parts, int N, float two, float* __restrict__ irr)
+// out[q][t] = irt_scale of (partial[part][q][k][3], the texel's part sums, added in part order) for the K classes q of the Nt-texel planes of `out`; K = 1:
+// the one irradiance texture of launch_irt, K > 1: the classes of launch_irt_split (irtsplit.hip)
+__global__ __launch_bounds__(256) void irt_combine_kernel(const float* __restrict__ partial, const int32_t* __restrict__ ids, int64_t n_ids, int64_t Nt, int K,
+                                                          int parts, int N, float two, float* __restrict__ out)
 {
-    const float pi = 3.141592653589793f;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < 3 * n_ids; e += (int64_t)gridDim.x * 256) {
-        const int64_t k = e / 3;
-        const int c = (int)(e - 3 * k);
+    const int64_t per_class = 3 * n_ids, total = per_class * K;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t q = e / per_class, r = e - q * per_class;
+        const int64_t k = r / 3;
+        const int c = (int)(r - 3 * k);
         float a = partial[e];
-        for (int p = 1; p < parts; p++) a += partial[(int64_t)p * n_ids * 3 + e];
+        for (int p = 1; p < parts; p++) a += partial[(int64_t)p * total + e];
         const int64_t t = ids ? (int64_t)ids[k] : k;
-        irr[3 * t + c] = ((a * two) * pi) / (float)N;
+        out[(q * Nt + t) * 3 + c] = irt_scale(a, two, N);
     }
+}
+
+hipError_t launch_irt_combine(const float* partial, const int32_t* ids, int64_t n_ids, int64_t Nt, int K, int parts, int N, float two, float* out, hipStream_t st)
+{
+    hipLaunchKernelGGL(irt_combine_kernel, dim3(grid_capped(256, 3 * n_ids * K)), dim3(256), 0, st, partial, ids, n_ids, Nt, K, parts, N, two, out);
+    return hipGetLastError();
 }
 
 // Retiled copies of the radiance texture for the hit shader (device_common.h shade_hit): same floats, other addresses.
@@ -699,17 +690,15 @@ IrtPlan irt_plan(const SceneDev& sc, int64_t n_ids, int N)
     return p;
 }
 
-template <typename K>
+// (`more`: what a kernel takes behind the arguments the IrT kernels share -- irt_stream_kernel's refill_at)
+template <typename K, typename... More>
 static void irt_launch(K kernel, int64_t waves_wanted, const SceneDev& sc, const float* pos, const float* nrm, const float* shift,
                        const int32_t* ids, int64_t n_ids, int N, int l2, int mode, float* irr, unsigned long long* stats,
-                       unsigned long long* work, float* partial, int log2parts, hipStream_t st)
+                       unsigned long long* work, float* partial, int log2parts, hipStream_t st, More... more)
 {
-    // persistent grid: exactly the workgroups that are co-resident, each wave strides over the texel list
-    const int64_t want = (waves_wanted + (kBlock / 64) - 1) / (kBlock / 64);
-    int grid = resident_grid(kernel, kBlock);
-    if (want < grid) grid = (int)want;
+    int grid = persistent_grid(kernel, waves_wanted, kBlock);
     if (const int cap = env().irt_grid_cap; cap > 0 && grid > cap) grid = cap;            // occupancy sweeps only (any grid gives the same result: the waves pull chunks)
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n_ids, N, l2, mode, irr, stats, work, partial, log2parts);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n_ids, N, l2, mode, irr, stats, work, partial, log2parts, more...);
 }
 
 size_t irt_scratch_bytes(const SceneDev& sc, int64_t n_ids, int N)
@@ -736,8 +725,6 @@ hipError_t launch_irt(const SceneDev& sc, const float* pos, const float* nrm, co
 #else
     constexpr bool probe_group = false;
 #endif
-#define TEXIR_IRT(WAVES, L2, NAME, ...) { if (stats && !probe_group) irt_launch(NAME<true, __VA_ARGS__>, WAVES, sc, pos, nrm, shift, ids, n_ids, N, L2, mode, irr, stats, work, partial, log2parts, st); \
-                                        else irt_launch(NAME<false, __VA_ARGS__>, WAVES, sc, pos, nrm, shift, ids, n_ids, N, L2, mode, irr, stats, work, partial, log2parts, st); }
     const int per_wave = plan.per_wave;
     float* partial = nullptr;
     const int log2parts = plan.log2parts;
@@ -757,25 +744,21 @@ hipError_t launch_irt(const SceneDev& sc, const float* pos, const float* nrm, co
         if (scratch) partial = scratch;                  // (caller-owned: the form a recorded hipGraph uses -- texir_scene_reserve_scratch)
         else if ((e = hipMallocAsync((void**)&partial, bytes, st)) != hipSuccess) return e;
     }
-    if (!sc.nodes4) TEXIR_IRT(n_ids, l2, irt_kernel, 2)                                        // deep binary tree (capi.hip fallback)
-    else if (per_wave == 1) TEXIR_IRT(n_ids, l2, irt_kernel, 4)
-    else if (env().irt_refill && pow2 && log2parts > 0) {
-        // compaction by refill (A/B switch TEXIR_IRT_REFILL = lanes that must be idle before a refill)
-        const int64_t waves = ((n_ids + 63) / 64) << log2parts;
-        const int64_t want = (waves + (kBlock / 64) - 1) / (kBlock / 64);
-        if (stats) {
-            int grid = resident_grid(irt_stream_kernel<true, 4>, kBlock); if (want < grid) grid = (int)want;
-            hipLaunchKernelGGL((irt_stream_kernel<true, 4>), dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n_ids, N, l2, mode, irr, stats, work, partial, log2parts, env().irt_refill);
-        } else {
-            int grid = resident_grid(irt_stream_kernel<false, 4>, kBlock); if (want < grid) grid = (int)want;
-            hipLaunchKernelGGL((irt_stream_kernel<false, 4>), dim3(grid), dim3(kBlock), 0, st, sc, pos, nrm, shift, ids, n_ids, N, l2, mode, irr, stats, work, partial, log2parts, env().irt_refill);
-        }
-    }
-    else TEXIR_IRT(((n_ids + 63) / 64) << log2parts, pow2 ? l2 : -1, irt_group_kernel, 4, 6)   // any N (natural sample order if not 2^k)
-#undef TEXIR_IRT
+    // (the counting form with `stats`, except where a probe build keeps its clocks in the shipped form)
+    auto go = [&](auto counting, auto plain, int64_t waves, int L2, auto... more) {
+        if (stats && !probe_group) irt_launch(counting, waves, sc, pos, nrm, shift, ids, n_ids, N, L2, mode, irr, stats, work, partial, log2parts, st, more...);
+        else irt_launch(plain, waves, sc, pos, nrm, shift, ids, n_ids, N, L2, mode, irr, stats, work, partial, log2parts, st, more...);
+    };
+    const int64_t chunks = ((n_ids + 63) / 64) << log2parts;                                       // of the 64-texel forms
+    if (!sc.nodes4) go(irt_kernel<true, 2>, irt_kernel<false, 2>, n_ids, l2);                      // deep binary tree (capi.hip fallback)
+    else if (per_wave == 1) go(irt_kernel<true, 4>, irt_kernel<false, 4>, n_ids, l2);
+    // compaction by refill (A/B switch TEXIR_IRT_REFILL = lanes that must be idle before a refill)
+    else if (env().irt_refill && pow2 && log2parts > 0) go(irt_stream_kernel<true, 4>, irt_stream_kernel<false, 4>, chunks, l2, env().irt_refill);
+    else go(irt_group_kernel<true, 4, 6>, irt_group_kernel<false, 4, 6>, chunks, pow2 ? l2 : -1);  // any N (natural sample order if not 2^k)
     if (log2parts) {
-        hipLaunchKernelGGL(irt_combine_kernel, dim3(grid_capped(256, 3 * n_ids)), dim3(256), 0, st, partial, ids, n_ids, 1 << log2parts, N, (mode & kEstimatorCosine) ? 1.f : 2.f, irr);
+        const hipError_t launched = launch_irt_combine(partial, ids, n_ids, 0 /*one class: no plane stride*/, 1, 1 << log2parts, N, (mode & kEstimatorCosine) ? 1.f : 2.f, irr, st);
         if (!scratch && (e = hipFreeAsync(partial, st)) != hipSuccess) return e;
+        return launched;
     }
     return hipGetLastError();
 }

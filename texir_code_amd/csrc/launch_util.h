@@ -23,6 +23,16 @@ inline int resident_grid(K kernel, int block)
     return cus * per_cu;
 }
 
+// persistent grid of a kernel whose waves (block / 64 per workgroup) stride over or pull `waves_wanted` pieces of work: exactly the workgroups that are
+// co-resident, fewer where the work does not fill them
+template <typename K>
+inline int persistent_grid(K kernel, int64_t waves_wanted, int block)
+{
+    const int64_t want = (waves_wanted + (block / 64) - 1) / (block / 64);
+    const int grid = resident_grid(kernel, block);
+    return want < grid ? (int)want : grid;
+}
+
 // log2 of a power of two; 0 for anything else
 inline int ilog2_exact(int N) { if (N <= 0 || (N & (N - 1))) return 0; int l = 0; while ((1 << l) < N) l++; return l; }
 
