@@ -356,7 +356,9 @@ TEXIR_API int texir_adam_step_tex_dev(float* param, const float* grad, const uin
  * textures with separate dr.texture calls, models/mat_nvdiffrast.py:131-139, and steps them with one torch.optim.Adam) --------------------------------------
  * A step over k material textures launches k x (mip build + tail, fetch, gather, fold, Adam); these entry points take up to TEXIR_MAX_BATCH jobs and issue ONE
  * launch per kind (blocks are dealt to the jobs by block index; every job keeps its own sizes and channel count).  Each job's result is bit-identical to the
- * corresponding single-texture entry point above.  Errors of these three functions are reported through texir_batch_last_error() (thread-local). */
+ * corresponding single-texture entry point above.  Errors of these functions are reported through texir_batch_last_error() (thread-local), which returns the
+ * library's one error text: the same string as texir_last_error().  (It used to be a text of its own: since the two were joined, texir_last_error() after a failed
+ * batched call holds that call's message too, where it once kept whatever an earlier call had left.) */
 #define TEXIR_MAX_BATCH 4
 TEXIR_API const char* texir_batch_last_error(void);
 

@@ -108,9 +108,10 @@ def test_header_and_signatures():
     # the bounds the reference uses are the header's
     for text in ("|d dd| <= 5 u dd", "|d ns| <= 3 u N1", "|d nn| <= 3 u nn", "6 u N1 |ns| + u ns^2 + 9 u c^2 nn_t nn_s", "|dd - r2| <= 5 u dd + u r2"):
         assert text in hdr, text
-    lib_py = open(os.path.join(ROOT, "texir_code_amd", "_lib.py")).read()
-    assert 'sig["texir_atlas_fill"]' in lib_py and "texir_atlas_fill_workspace_bytes.argtypes" in lib_py
+    import ctypes
     from texir_code_amd import _lib
+    table = _lib.signatures()
+    assert len(table["texir_atlas_fill"]) == 16 and table["texir_atlas_fill_workspace_bytes"] == (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64])
     L = _lib.lib()
     assert len(L.texir_atlas_fill.argtypes) == 16 and L.texir_atlas_fill_workspace_bytes.restype is not None
     # the workspace grows with the sources and never shrinks below the grid's own arrays

@@ -55,3 +55,33 @@ def test_job_structures_have_the_headers_layout(tmp_path):
         for fname, _ in cls._fields_:
             assert int(got["%s.%s" % (cname, fname)]) == getattr(cls, fname).offset, (cname, fname)
     assert int(got["TEXIR_MAX_BATCH"]) == _lib.MAX_BATCH
+
+
+def declared_parameter_counts():
+    """name -> number of parameters of every TEXIR_API declaration of the header: the commas at parenthesis depth one, plus one; `(void)` is none"""
+    txt = open(os.path.join(ROOT, "include", "texir_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    counts = {}
+    for m in re.finditer(r"TEXIR_API\s+[\w\s\*]+?\b(texir_\w+)\s*\(", txt):
+        depth, commas, i = 1, 0, m.end()
+        while depth:
+            c = txt[i]
+            depth += (c == "(") - (c == ")")
+            commas += c == "," and depth == 1
+            i += 1
+        inside = txt[m.end():i - 1].strip()
+        counts[m.group(1)] = 0 if inside in ("", "void") else commas + 1
+    return counts
+
+
+def test_ctypes_table_matches_the_header():
+    """a wrong argument count in ctypes passes garbage without an error: every declared function has an entry in _lib.signatures(), with as many
+    argument types as the declaration has parameters, and the table lists them in the header's order"""
+    from texir_code_amd import _lib
+    counts = declared_parameter_counts()
+    assert sorted(counts) == declared_symbols() and len(counts) >= 60
+    table = _lib.signatures()
+    assert list(table) == list(counts), "the table is not in the header's order, or lacks / invents a function"
+    for name, entry in table.items():
+        args = entry[1] if isinstance(entry, tuple) else entry
+        assert len(args) == counts[name], (name, len(args), counts[name])

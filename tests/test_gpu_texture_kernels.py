@@ -1,4 +1,4 @@
-"""The texture path of csrc/material.hip -- mip build, level selection, wrap-bilinear taps, fetch, the three backward forms and the gradient folds --
+"""The texture path of csrc/material.hip (the file holds nothing else: the G-buffer is csrc/gbuffer.hip, the optimiser csrc/adam.hip) -- mip build, level selection, wrap-bilinear taps, fetch, the three backward forms and the gradient folds --
 against the float64 restatement of tests/texture_cases.py, element by element inside a bound derived from a float32 rounding model (K = 4, fixed
 before the first run; see texture_cases for the derivation).  No pixel and no texel is excluded from any comparison.  Every form of the code
 (pyramid and TEXIR_MIP_PER_LEVEL=1, scatter / deferred / gather with fold_to_level 0, 1, 2, single and batched launches) is compared with the

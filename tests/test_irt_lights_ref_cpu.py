@@ -203,9 +203,8 @@ def test_header_declares_and_the_loader_binds_the_entry_point():
     assert n_args == 14
     for word in ("FLOAT32 OPERATION SEQUENCE", "ROUNDING BOUND", "shift_wrap_clamp", "t_max"):
         assert word in hdr[hdr.index("inserted emitters"):m.start()]
-    src = open(os.path.join(ROOT, "texir_code_amd", "_lib.py")).read()
-    m = re.search(r'sig\["texir_irt_lights"\] = \[([^\]]*)\]', src)
-    assert m and len(m.group(1).split(",")) == n_args
+    from texir_code_amd import _lib
+    assert len(_lib.signatures()["texir_irt_lights"]) == n_args
     mk = open(os.path.join(ROOT, "texir_code_amd", "csrc", "Makefile")).read()
     assert mk.count("irtlight.hip") == 2
     from texir_code_amd import scene

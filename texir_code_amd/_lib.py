@@ -20,6 +20,85 @@ def build():
     return LIB_PATH
 
 
+def signatures():
+    """every TEXIR_API function of include/texir_hip.h, in the header's order: name -> argtypes, or (restype, argtypes) where the function does not
+    return an int32 status (tests/test_cabi.py holds the table against the header)"""
+    vp, i32, i64, f32, text = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_char_p
+    bake = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
+    lights = [vp, vp, vp, vp, vp, i64, i64, vp, i32, i32, f32, vp, vp, vp]
+    return {
+        "texir_last_error": (text, []),
+        "texir_version": [],
+        "texir_reload_env": [],
+        "texir_env_switch": [text, C.POINTER(i32)],
+        "texir_scene_create": [vp, i32, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp)],
+        "texir_scene_destroy": [vp],
+        "texir_scene_set_texture": [vp, vp, i32, i32, i32, vp],
+        "texir_scene_texture_layout": [vp, vp],
+        "texir_texel_pack": [vp, i64, vp, vp],
+        "texir_texel_unpack": [vp, i64, vp],
+        "texir_scene_info": [vp, vp],
+        "texir_scene_tune": [vp, vp, vp, vp, vp, i64, i32, i32, vp],
+        "texir_scene_scheduler": [vp, vp],
+        "texir_scene_prefetch": [vp, i32, i32, vp],
+        "texir_trace_shade": [vp, vp, vp, i64, f32, vp, vp, vp, vp, vp],
+        "texir_trace_occluded": [vp, vp, vp, i64, f32, f32, vp, vp, vp],
+        "texir_generate_dir": [vp, vp, vp, i64, i32, i32, vp, vp],
+        "texir_irt_generate": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, vp, vp],
+        "texir_scene_reserve_scratch": [vp, i64, i32],
+        "texir_irt_split_workspace_bytes": (i64, [i64, i32, i32]),
+        "texir_irt_split": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, i32, vp, vp, i64, vp],
+        "texir_irt_kernel_name": [vp, i64, i32, text, i32],
+        "texir_spec_forward": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp],
+        "texir_spec_forward_train": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp, vp],
+        "texir_spec_backward_ws": [vp, vp, vp, vp, i64, i32, vp, vp, vp],
+        "texir_spec_backward": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp, vp, vp],
+        "texir_diffuse_irradiance": [vp, vp, vp, vp, i64, i32, i32, vp, vp],
+        "texir_loss_workspace_bytes": (i64, [i64, i32, i32]),
+        "texir_loss_forward": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+        "texir_scene_set_corner_normals": [vp, vp],
+        "texir_gbuffer_cast": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+        "texir_mip_levels": [i32, i32, i32],
+        "texir_mip_elems": (i64, [i32, i32, i32, i32]),
+        "texir_mip_build": [vp, vp, i32, i32, i32, i32, i32, vp],
+        "texir_tex_fetch_forward": [vp, vp, i32, i32, i32, i32, vp, vp, i32, i64, vp, vp],
+        "texir_tex_fetch_backward": [vp, vp, i32, i32, i32, i32, vp, vp, i32, i64, vp, vp],
+        "texir_tex_fetch_backward_deferred": [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp],
+        "texir_tex_taps": [i32, i32, i32, i32, vp, vp, i32, i64, vp, vp, vp],
+        "texir_tex_gather_backward": [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp],
+        "texir_adam_step": [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, f32, f32, vp],
+        "texir_adam_step_tex": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, i32, f32, f32, vp],
+        "texir_adam_tick": [vp, vp, i32, C.c_uint64, vp],
+        "texir_adam_step_dev": [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp],
+        "texir_adam_step_tex_dev": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, f32, f32, f32, f32, f32, vp],
+        "texir_batch_last_error": (text, []),
+        "texir_tex_fetch_forward_batch": [vp, i32, vp],
+        "texir_tex_gather_backward_batch": [vp, i32, vp],
+        "texir_grad_add_masked": [vp, vp, vp, i64, i32, vp],
+        "texir_adam_step_tex_dev_batch": [vp, i32, vp],
+        "texir_texture_pad_workspace_bytes": (i64, [i32, i32]),
+        "texir_texture_pad": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+        "texir_texture_denoise": [vp, i32, i32, vp, vp, i32, f32, f32, f32, vp, vp, vp],
+        "texir_texel_gbuffer_workspace_bytes": [vp, i32, i32, C.POINTER(i64)],
+        "texir_texel_gbuffer": [vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp],
+        "texir_atlas_bake": bake,
+        "texir_atlas_bake_any": bake,
+        "texir_atlas_gather": [vp, vp, vp, i64, i64, vp, i32, i32, i32, i32, vp, vp],
+        "texir_atlas_fill_workspace_bytes": (i64, [i64, i64]),
+        "texir_atlas_fill_cell": (f32, [vp, i64, f32]),
+        "texir_atlas_fill": [vp, vp, i64, vp, i64, vp, i64, vp, f32, f32, f32, vp, vp, vp, vp, vp],
+        "texir_irt_lights": lights,
+        "texir_irt_lights_any": lights,
+        "texir_png_unfilter": [vp, i32, i32, i32, vp],
+        "texir_hdr_decode_scanlines": (i64, [vp, i64, i32, i32, vp]),
+        "texir_rgbe_encode": [vp, i64, vp],
+        "texir_hdr_encode_rle": (i64, [vp, i32, i32, vp, i64]),
+        "texir_rgbe_decode": [vp, i64, vp],
+        "texir_obj_parse": [vp, i64, C.POINTER(vp), vp],
+        "texir_obj_take": [vp, vp, vp, vp, vp, vp, vp],
+    }
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -34,92 +113,9 @@ def lib():
         if os.path.exists(tl):
             C.CDLL(tl, mode=C.RTLD_GLOBAL)
         L = C.CDLL(LIB_PATH)
-        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-        L.texir_last_error.restype = C.c_char_p
-        L.texir_version.restype = i32
-        sig = {
-            "texir_scene_create": [vp, i32, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp)],
-            "texir_scene_destroy": [vp],
-            "texir_scene_set_texture": [vp, vp, i32, i32, i32, vp],
-            "texir_scene_texture_layout": [vp, vp],
-            "texir_texel_pack": [vp, i64, vp, vp],
-            "texir_texel_unpack": [vp, i64, vp],
-            "texir_scene_info": [vp, vp],
-            "texir_scene_scheduler": [vp, vp],
-            "texir_scene_tune": [vp, vp, vp, vp, vp, i64, i32, i32, vp],
-            "texir_scene_prefetch": [vp, i32, i32, vp],
-            "texir_scene_reserve_scratch": [vp, i64, i32],
-            "texir_trace_shade": [vp, vp, vp, i64, f32, vp, vp, vp, vp, vp],
-            "texir_trace_occluded": [vp, vp, vp, i64, f32, f32, vp, vp, vp],
-            "texir_generate_dir": [vp, vp, vp, i64, i32, i32, vp, vp],
-            "texir_irt_generate": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, vp, vp],
-            "texir_spec_forward": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp],
-            "texir_spec_backward": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp, vp, vp],
-            "texir_spec_forward_train": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp, vp],
-            "texir_spec_backward_ws": [vp, vp, vp, vp, i64, i32, vp, vp, vp],
-            "texir_diffuse_irradiance": [vp, vp, vp, vp, i64, i32, i32, vp, vp],
-        }
-        sig["texir_irt_kernel_name"] = [vp, i64, i32, C.c_char_p, i32]
-        L.texir_irt_split_workspace_bytes.argtypes = [i64, i32, i32]
-        L.texir_irt_split_workspace_bytes.restype = i64
-        sig["texir_irt_split"] = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, i32, vp, vp, i64, vp]
-        sig["texir_loss_forward"] = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-        sig["texir_scene_set_corner_normals"] = [vp, vp]
-        sig["texir_gbuffer_cast"] = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-        sig["texir_mip_build"] = [vp, vp, i32, i32, i32, i32, i32, vp]
-        sig["texir_tex_fetch_forward"] = [vp, vp, i32, i32, i32, i32, vp, vp, i32, i64, vp, vp]
-        sig["texir_tex_fetch_backward"] = [vp, vp, i32, i32, i32, i32, vp, vp, i32, i64, vp, vp]
-        sig["texir_adam_step"] = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, f32, f32, vp]
-        sig["texir_tex_fetch_backward_deferred"] = [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp]
-        sig["texir_tex_taps"] = [i32, i32, i32, i32, vp, vp, i32, i64, vp, vp, vp]
-        sig["texir_tex_gather_backward"] = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp]
-        sig["texir_adam_step_tex"] = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, i32, f32, f32, vp]
-        sig["texir_adam_tick"] = [vp, vp, i32, C.c_uint64, vp]
-        sig["texir_adam_step_dev"] = [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp]
-        sig["texir_adam_step_tex_dev"] = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, f32, f32, f32, f32, f32, vp]
-        L.texir_batch_last_error.restype = C.c_char_p
-        sig["texir_grad_add_masked"] = [vp, vp, vp, i64, i32, vp]
-        sig["texir_tex_fetch_forward_batch"] = [vp, i32, vp]
-        sig["texir_tex_gather_backward_batch"] = [vp, i32, vp]
-        sig["texir_adam_step_tex_dev_batch"] = [vp, i32, vp]
-        L.texir_reload_env.argtypes = []
-        L.texir_reload_env.restype = i32
-        L.texir_mip_levels.argtypes = [i32, i32, i32]
-        L.texir_mip_levels.restype = i32
-        L.texir_mip_elems.argtypes = [i32, i32, i32, i32]
-        L.texir_mip_elems.restype = i64
-        L.texir_loss_workspace_bytes.argtypes = [i64, i32, i32]
-        L.texir_loss_workspace_bytes.restype = i64
-        L.texir_texture_pad_workspace_bytes.argtypes = [i32, i32]
-        L.texir_texture_pad_workspace_bytes.restype = i64
-        sig["texir_texture_pad"] = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-        sig["texir_texture_denoise"] = [vp, i32, i32, vp, vp, i32, f32, f32, f32, vp, vp, vp]
-        sig["texir_texel_gbuffer_workspace_bytes"] = [vp, i32, i32, C.POINTER(i64)]
-        sig["texir_texel_gbuffer"] = [vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp]
-        sig["texir_atlas_bake"] = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
-        sig["texir_atlas_bake_any"] = sig["texir_atlas_bake"]
-        sig["texir_atlas_gather"] = [vp, vp, vp, i64, i64, vp, i32, i32, i32, i32, vp, vp]
-        L.texir_atlas_fill_workspace_bytes.argtypes = [i64, i64]
-        L.texir_atlas_fill_workspace_bytes.restype = i64
-        L.texir_atlas_fill_cell.argtypes = [vp, i64, f32]
-        L.texir_atlas_fill_cell.restype = f32
-        sig["texir_atlas_fill"] = [vp, vp, i64, vp, i64, vp, i64, vp, f32, f32, f32, vp, vp, vp, vp, vp]
-        sig["texir_irt_lights"] = [vp, vp, vp, vp, vp, i64, i64, vp, i32, i32, f32, vp, vp, vp]
-        sig["texir_irt_lights_any"] = sig["texir_irt_lights"]
-        sig["texir_png_unfilter"] = [vp, i32, i32, i32, vp]
-        L.texir_hdr_decode_scanlines.argtypes = [vp, i64, i32, i32, vp]
-        L.texir_hdr_decode_scanlines.restype = i64
-        L.texir_hdr_encode_rle.argtypes = [vp, i32, i32, vp, i64]
-        L.texir_hdr_encode_rle.restype = i64
-        sig["texir_env_switch"] = [C.c_char_p, C.POINTER(i32)]
-        sig["texir_rgbe_encode"] = [vp, i64, vp]
-        sig["texir_rgbe_decode"] = [vp, i64, vp]
-        sig["texir_obj_parse"] = [vp, i64, C.POINTER(vp), vp]
-        sig["texir_obj_take"] = [vp, vp, vp, vp, vp, vp, vp]
-        for name, args in sig.items():
+        for name, entry in signatures().items():
             fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = i32
+            fn.restype, fn.argtypes = entry if isinstance(entry, tuple) else (C.c_int32, entry)
         _LIB = L
     return _LIB
 

@@ -1,4 +1,4 @@
-// C-ABI of libtexir_hip.so (include/texir_hip.h).  Thin: argument checks, handle ownership, launches.
+// C-ABI of libtexir_hip.so (include/texir_hip.h), all of it but the host-side file codecs of io_native.cpp.  Thin: argument checks, handle ownership, launches.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -78,6 +78,30 @@ static int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(TEXIR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// is `st` being recorded into a hipGraph?  (`if_unknown`: what a failed query counts as -- its callers differ)
+static bool stream_capturing(hipStream_t st, bool if_unknown)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) return if_unknown;
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// the chunk counters of one launch: the scene's next slot, round-robin
+static unsigned long long* next_work_slot(const texir_scene* s)
+{
+    return s->d_work + (size_t)(s->work_next.fetch_add(1) % texir_scene::kWorkSlots) * 8 * kWorkStride;
+}
+
+// a cached device copy of the texture (install_texture): kept while its layout and size stay what they were, else freed and allocated anew -- never while recording
+static int resize_cached(void** buf, size_t* have_bytes, int* have_layout, size_t bytes, int layout, bool capturing)
+{
+    if (*buf && (*have_layout != layout || *have_bytes != bytes)) { HIP_TRY(hipFree(*buf)); *buf = nullptr; }
+    if (*buf) return TEXIR_OK;
+    if (capturing) return fail(TEXIR_ERR_INVALID, "texir_scene_set_texture: the stream is being captured and the float32 tiles are not allocated yet");
+    HIP_TRY(hipMalloc(buf, bytes)); *have_bytes = bytes; *have_layout = layout;
+    return TEXIR_OK;
+}
+
 // Chooses and fills the hit shader's copy of the radiance texture; d_tex (row-major float32 master) has been written on `st` already.
 // TEXIR_TEX_LAYOUT 4 (default) / 3: 4-byte shared-exponent texels when EVERY texel is three 8-bit integers times one power of two -- what an RGBE file
 // times 2^hdr_exposure always is (tracer_o3d_irt.py:77-81) -- decoding to the identical floats; any other texture (a float-valued synthetic one,
@@ -86,13 +110,11 @@ static int fail(int code, const char* fmt, ...)
 static int install_texture(texir_scene* s, hipStream_t st)
 {
     const int want = env().tex_layout, Ht = s->dev.Ht, Wt = s->dev.Wt;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    const bool capturing = stream_capturing(st, true);
     if ((want == 3 || want == 4) && !capturing && Ht < (1 << 16) && Wt < (1 << 16)) {
         int tx, ty;
         const size_t bytes = tex_pack_bytes(Ht, Wt, want, &tx, &ty);
-        if (s->d_tex_packed && (s->packed_layout != want || s->packed_bytes != bytes)) { HIP_TRY(hipFree(s->d_tex_packed)); s->d_tex_packed = nullptr; }
-        if (!s->d_tex_packed) { HIP_TRY(hipMalloc((void**)&s->d_tex_packed, bytes)); s->packed_bytes = bytes; s->packed_layout = want; }
+        if (int rc = resize_cached((void**)&s->d_tex_packed, &s->packed_bytes, &s->packed_layout, bytes, want, false)) return rc;
         if (!s->d_tex_flag) HIP_TRY(hipMalloc((void**)&s->d_tex_flag, sizeof(unsigned int)));
         HIP_TRY(launch_tex_pack(s->d_tex, s->d_tex_packed, Ht, Wt, want, s->d_tex_flag, st));
         unsigned int bad = 1;
@@ -107,17 +129,78 @@ static int install_texture(texir_scene* s, hipStream_t st)
     if (layout == 1 || layout == 2) {
         int tx, ty;
         const size_t bytes = tex_retile_bytes(Ht, Wt, layout, &tx, &ty);
-        if (s->d_tex_tiled && (s->tiled_layout != layout || s->tiled_bytes != bytes)) { HIP_TRY(hipFree(s->d_tex_tiled)); s->d_tex_tiled = nullptr; }
-        if (!s->d_tex_tiled) {
-            if (capturing) return fail(TEXIR_ERR_INVALID, "texir_scene_set_texture: the stream is being captured and the float32 tiles are not allocated yet");
-            HIP_TRY(hipMalloc((void**)&s->d_tex_tiled, bytes)); s->tiled_bytes = bytes; s->tiled_layout = layout;
-        }
+        if (int rc = resize_cached((void**)&s->d_tex_tiled, &s->tiled_bytes, &s->tiled_layout, bytes, layout, capturing)) return rc;
         HIP_TRY(launch_tex_retile(s->d_tex, s->d_tex_tiled, Ht, Wt, layout, st));
         s->dev.tex = s->d_tex_tiled; s->dev.tex_layout = layout; s->dev.tiles_x = tx;
     } else {
         s->dev.tex = s->d_tex; s->dev.tex_layout = 0; s->dev.tiles_x = 0;
     }
     return TEXIR_OK;
+}
+
+// ---- the argument rules of the texture side, each written once.  k = the job's index in a batched call (its messages say `job k: `), -1 = the single-texture
+// call, which fills a job structure and is held to the same rules ----
+static int fail_job(const char* fn, int k, const char* fmt, ...)
+{
+    char msg[384];
+    va_list ap; va_start(ap, fmt); vsnprintf(msg, sizeof(msg), fmt, ap); va_end(ap);
+    return k < 0 ? fail(TEXIR_ERR_INVALID, "%s: %s", fn, msg) : fail(TEXIR_ERR_INVALID, "%s: job %d: %s", fn, k, msg);
+}
+
+static int check_tex(const char* fn, int k, int H, int W, int C, int levels)
+{
+    if (H <= 0 || W <= 0 || C <= 0 || C > 4 || levels < 1 || levels > 16) return fail_job(fn, k, "bad texture H=%d W=%d C=%d levels=%d", H, W, C, levels);
+    if (levels > mip_levels(H, W, 15)) return fail_job(fn, k, "%d mip levels not available for %dx%d", levels, H, W);
+    return 0;
+}
+
+// (the single-texture call demands uv / out even at P = 0 and has no build_from to name)
+static int check_fetch_job(const char* fn, int k, const texir_tex_fetch_job& q)
+{
+    const bool batched = k >= 0, trilinear = q.filter_mode == 1;
+    if (!q.tex || ((!batched || q.P > 0) && (!q.uv || !q.out || (trilinear && !q.uv_da))) || (trilinear && q.levels > 1 && !q.mips_rest))
+        return fail_job(fn, k, "null argument");
+    if (q.filter_mode < 0 || q.filter_mode > 1 || q.P < 0 || q.build_from < -1 || q.build_from > 1)
+        return fail_job(fn, k, "bad filter_mode/P%s", batched ? "/build_from" : "");
+    if (q.build_from >= 0 && q.levels > 1 && !q.mips_rest) return fail_job(fn, k, "a build needs mips_rest");
+    return check_tex(fn, k, q.H, q.W, q.C, q.levels);
+}
+
+static int check_gather_job(const char* fn, int k, const texir_tex_gather_job& q)
+{
+    // d_tex may be NULL with defer_last_fold when no tap of the lists samples level 0 (then nothing is written there and the caller's
+    // optimiser step treats the level-0 gradient as identically zero)
+    if ((!q.d_tex && !q.defer_last_fold) || !q.d_out || (q.n_seg > 0 && (!q.seg_key || !q.seg_start || !q.seg_count || !q.pix || !q.weights)) || (q.filter_mode == 1 && q.levels > 1 && !q.grad_rest))
+        return fail_job(fn, k, "null argument");
+    if (q.filter_mode < 0 || q.filter_mode > 1 || q.n_seg < 0 || q.defer_last_fold < 0 || q.defer_last_fold > 2 || (q.defer_last_fold && (q.filter_mode != 1 || q.levels < 2))
+        || (q.defer_last_fold == 2 && (q.levels < 4 || (q.H & 3) || (q.W & 3))))
+        return fail_job(fn, k, "bad filter_mode/n_seg/defer_last_fold");
+    // (d_out2 and rest_mask: fields of the batched form alone)
+    if (q.d_out2 && env().mip_per_level) return fail_job(fn, k, "d_out2 is not available with TEXIR_MIP_PER_LEVEL=1");
+    if (q.rest_mask && q.defer_last_fold != 2) return fail_job(fn, k, "rest_mask needs defer_last_fold = 2");
+    if (q.rest_mask && env().mip_per_level) return fail_job(fn, k, "rest_mask is not available with TEXIR_MIP_PER_LEVEL=1 (the per-level folds read a cleared stack)");
+    return check_tex(fn, k, q.H, q.W, q.C, q.levels);
+}
+
+// step: the host-side step count of texir_adam_step_tex, which needs grad_level1 and no hyper; nullptr: the *_dev forms (level1_mask: a field of the batched form alone)
+static int check_adam_tex_job(const char* fn, int k, const texir_adam_tex_job& q, const int32_t* step = nullptr)
+{
+    if (!q.param || !q.exp_avg || !q.exp_avg_sq || (step ? !q.grad_level1 : ((!q.grad_level1 && !q.grad_level2) || !q.hyper))) return fail_job(fn, k, "null argument");
+    if (q.H < 2 || q.W < 2 || (q.H & 1) || (q.W & 1) || q.C < 1 || q.C > 4 || (step && *step < 1)) return fail_job(fn, k, "bad H/W/C%s", step ? "/step" : "");
+    if (q.grad_level2 && ((q.H & 3) || (q.W & 3))) return fail_job(fn, k, "a level-2 gradient needs H and W divisible by 4");
+    if (q.level1_mask && !q.grad_level2) return fail_job(fn, k, "level1_mask needs grad_level2");
+    return 0;
+}
+
+template <class Job, class Check>
+static int batch_call(const char* fn, const Job* jobs, int n, void* stream, Check check, hipError_t (*launch)(const Job*, int, hipStream_t))
+{
+    if (n < 0 || n > TEXIR_MAX_BATCH || (n > 0 && !jobs)) return fail(TEXIR_ERR_INVALID, "%s: 0..%d jobs (got %d)", fn, TEXIR_MAX_BATCH, n);
+    for (int k = 0; k < n; k++)
+        if (int rc = check(fn, k, jobs[k])) return rc;
+    if (n == 0) return TEXIR_OK;
+    const hipError_t e = launch(jobs, n, (hipStream_t)stream);
+    return e == hipSuccess ? TEXIR_OK : fail(TEXIR_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
 }
 
 extern "C" {
@@ -147,40 +230,36 @@ int texir_scene_create(const float* verts, int32_t V, const int32_t* tris, int32
     s->device = device; s->n_nodes = (int64_t)h.nodes.size(); s->n_tris = T; s->max_depth = h.max_depth;
     s->tex_bytes = sizeof(float) * 3 * (size_t)Ht * Wt;
     auto bail = [&](hipError_t e, const char* what) { texir_scene_destroy(s); return fail(TEXIR_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); };
-    hipError_t e;
+    // one device buffer of the scene: allocated and, where there is a host source, filled
+    auto alloc_upload = [&](void** dst, const void* src, size_t bytes, const char* what) -> int {
+        hipError_t e = hipMalloc(dst, bytes);
+        if (e != hipSuccess) return bail(e, (std::string("hipMalloc ") + what).c_str());
+        if (src && (e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, (std::string("upload ") + what).c_str());
+        return TEXIR_OK;
+    };
+    int rc = TEXIR_OK;
     // traversal tree: 4-wide quantised by default (TEXIR_BVH_WIDTH=2 keeps the binary tree); falls back to binary when the wide
     // tree's worst-case stack (3 pushes per level) would not fit the traversal stack
     const int want_w = env().bvh_width;
     s->width = (want_w == 4 && 3 * h.max_depth4 + 2 <= kStackCap) ? 4 : 2;
     if (s->width == 4) {
         s->n_nodes4 = (int64_t)h.nodes4.size(); s->max_depth = h.max_depth4;
-        if ((e = hipMalloc(&s->d_nodes4, h.nodes4.size() * sizeof(GpuNode4))) != hipSuccess) return bail(e, "hipMalloc nodes4");
-        if ((e = hipMemcpy(s->d_nodes4, h.nodes4.data(), h.nodes4.size() * sizeof(GpuNode4), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "upload nodes4");
+        if ((rc = alloc_upload(&s->d_nodes4, h.nodes4.data(), h.nodes4.size() * sizeof(GpuNode4), "nodes4"))) return rc;
         // the float form of the same nodes, read by wave-uniform node steps through the scalar cache (TEXIR_UNIFORM_FLOAT=0: A/B switch)
-        if (env().uniform_float) {
-            if ((e = hipMalloc(&s->d_nodes4f, h.nodes4f.size() * sizeof(GpuNode4F))) != hipSuccess) return bail(e, "hipMalloc nodes4f");
-            if ((e = hipMemcpy(s->d_nodes4f, h.nodes4f.data(), h.nodes4f.size() * sizeof(GpuNode4F), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "upload nodes4f");
-        }
+        if (env().uniform_float && (rc = alloc_upload(&s->d_nodes4f, h.nodes4f.data(), h.nodes4f.size() * sizeof(GpuNode4F), "nodes4f"))) return rc;
     }
-    if ((e = hipMalloc(&s->d_nodes, h.nodes.size() * sizeof(GpuNode))) != hipSuccess) return bail(e, "hipMalloc nodes");
-    if ((e = hipMalloc(&s->d_tris, h.tris.size() * sizeof(GpuTri))) != hipSuccess) return bail(e, "hipMalloc tris");
-    if (!h.quads.empty()) {
-        if ((e = hipMalloc(&s->d_quads, h.quads.size() * sizeof(GpuQuad))) != hipSuccess) return bail(e, "hipMalloc quads");
-        if ((e = hipMemcpy(s->d_quads, h.quads.data(), h.quads.size() * sizeof(GpuQuad), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "upload quads");
-    }
-    if (!h.uvs.empty() && (e = hipMalloc(&s->d_uvs, h.uvs.size() * sizeof(GpuTriUV))) != hipSuccess) return bail(e, "hipMalloc uvs");
-    if ((e = hipMalloc((void**)&s->d_tex, s->tex_bytes)) != hipSuccess) return bail(e, "hipMalloc texture");
-    if ((e = hipMalloc((void**)&s->d_work, texir_scene::kWorkSlots * 8 * kWorkStride * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc work counters");
-    if ((e = hipMemcpy(s->d_nodes, h.nodes.data(), h.nodes.size() * sizeof(GpuNode), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "upload nodes");
-    if ((e = hipMemcpy(s->d_tris, h.tris.data(), h.tris.size() * sizeof(GpuTri), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "upload tris");
-    if (!h.uvs.empty() && (e = hipMemcpy(s->d_uvs, h.uvs.data(), h.uvs.size() * sizeof(GpuTriUV), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "upload uvs");
-    if ((e = hipMemcpy(s->d_tex, hdr_tex, s->tex_bytes, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "upload texture");
+    if ((rc = alloc_upload(&s->d_nodes, h.nodes.data(), h.nodes.size() * sizeof(GpuNode), "nodes"))) return rc;
+    if ((rc = alloc_upload(&s->d_tris, h.tris.data(), h.tris.size() * sizeof(GpuTri), "tris"))) return rc;
+    if (!h.quads.empty() && (rc = alloc_upload(&s->d_quads, h.quads.data(), h.quads.size() * sizeof(GpuQuad), "quads"))) return rc;
+    if (!h.uvs.empty() && (rc = alloc_upload(&s->d_uvs, h.uvs.data(), h.uvs.size() * sizeof(GpuTriUV), "uvs"))) return rc;
+    if ((rc = alloc_upload((void**)&s->d_tex, hdr_tex, s->tex_bytes, "texture"))) return rc;
+    if ((rc = alloc_upload((void**)&s->d_work, nullptr, texir_scene::kWorkSlots * 8 * kWorkStride * sizeof(unsigned long long), "work counters"))) return rc;
     s->dev.nodes4 = (const float4*)s->d_nodes4; s->dev.nodes4f = (const float4*)s->d_nodes4f;
     s->dev.nodes = (const float4*)s->d_nodes; s->dev.tris = (const float4*)s->d_tris; s->dev.quads = (const float4*)s->d_quads; s->dev.uvs = (const float4*)s->d_uvs;
     s->dev.tex = s->d_tex; s->dev.Ht = Ht; s->dev.Wt = Wt; s->dev.tex_layout = 0; s->dev.tiles_x = 0; s->dev.sched_weight = 0;
     // hit-shader copy of the texture (install_texture): 4-byte texels when they decode to the identical floats, else float32 tiles
-    if (const int rc = install_texture(s, 0)) { texir_scene_destroy(s); return rc; }
-    if ((e = hipStreamSynchronize(0)) != hipSuccess) return bail(e, "texture layout");
+    if ((rc = install_texture(s, 0))) { texir_scene_destroy(s); return rc; }
+    if (const hipError_t e = hipStreamSynchronize(0); e != hipSuccess) return bail(e, "texture layout");
     *out = s;
     return TEXIR_OK;
 }
@@ -189,20 +268,9 @@ int texir_scene_destroy(texir_scene* s)
 {
     if (!s) return TEXIR_OK;
     (void)hipSetDevice(s->device);
-    if (s->d_nodes4) (void)hipFree(s->d_nodes4);
-    if (s->d_nodes4f) (void)hipFree(s->d_nodes4f);
-    if (s->d_nodes) (void)hipFree(s->d_nodes);
-    if (s->d_tris) (void)hipFree(s->d_tris);
-    if (s->d_quads) (void)hipFree(s->d_quads);
-    if (s->d_uvs) (void)hipFree(s->d_uvs);
-    if (s->d_tex) (void)hipFree(s->d_tex);
-    if (s->d_tex_tiled) (void)hipFree(s->d_tex_tiled);
-    if (s->d_tex_packed) (void)hipFree(s->d_tex_packed);
-    if (s->d_tex_flag) (void)hipFree(s->d_tex_flag);
-    if (s->d_cnrm) (void)hipFree(s->d_cnrm);
-    if (s->d_scratch) (void)hipFree(s->d_scratch);
+    void* const owned[] = {s->d_nodes4, s->d_nodes4f, s->d_nodes, s->d_tris, s->d_quads, s->d_uvs, s->d_tex, s->d_tex_tiled, s->d_tex_packed, s->d_tex_flag, s->d_cnrm, s->d_scratch, s->d_work};
+    for (void* p : owned) if (p) (void)hipFree(p);
     for (float* p : s->retired_scratch) (void)hipFree(p);
-    if (s->d_work) (void)hipFree(s->d_work);
     delete s;
     return TEXIR_OK;
 }
@@ -287,12 +355,11 @@ int texir_scene_tune(const texir_scene* s, const float* pos, const float* nrm, c
     int w = env().sched_weight;
     double util = -1.0;
     if (w == 0 && texel_ids && n_ids >= 65536 && N >= 256 && s->width == 4) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+        if (stream_capturing((hipStream_t)stream, true)) {
             s->sched_state.store(0);                 // a blocking measurement cannot be recorded: stay undecided, keep the default weight
             return fail(TEXIR_ERR_INVALID, "texir_scene_tune: the stream is being captured (tune the scene before recording)");
         }
-        unsigned long long* work = s->d_work + (size_t)(s->work_next.fetch_add(1) % texir_scene::kWorkSlots) * 8 * kWorkStride;
+        unsigned long long* work = next_work_slot(s);
         const int64_t count = 16384, first = ((n_ids / 3) / 64) * 64;
         const hipError_t e = irt_probe_node_utilisation(s->dev, pos, nrm, shift, texel_ids, first, count, N, mode, work, (hipStream_t)stream, &util);
         if (e != hipSuccess) { s->sched_state.store(0); return fail(TEXIR_ERR_HIP, "texir_scene_tune: %s", hipGetErrorString(e)); }
@@ -358,14 +425,13 @@ int texir_irt_generate(const texir_scene* s, const float* pos, const float* nrm,
     if (N <= 0 || Nt < 0 || n_ids < 0) return fail(TEXIR_ERR_INVALID, "texir_irt_generate: bad sizes N=%d Nt=%lld n_ids=%lld", N, (long long)Nt, (long long)n_ids);
     if (Nt >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "texir_irt_generate: Nt too large");
     int64_t n = texel_ids ? n_ids : Nt;
-    unsigned long long* work = s->d_work + (size_t)(s->work_next.fetch_add(1) % texir_scene::kWorkSlots) * 8 * kWorkStride;
+    unsigned long long* work = next_work_slot(s);
     // (No measurement and no synchronisation in here: the phase scheduler's weight is whatever texir_scene_tune / TEXIR_SCHED_WEIGHT has decided for
     // the scene, 2 until then.  The texture is the same bits either way.)
     // A launch that is being RECORDED into a hipGraph must not allocate: stream-ordered allocations inside a recorded graph gave wrong partial sums in
     // some replays on this stack (ROCm 7.2: profiles/r04, graph replay probe).  It uses the scratch the caller reserved on the scene beforehand.
     float* scratch = nullptr;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+    if (stream_capturing((hipStream_t)stream, false)) {
         const size_t need = irt_scratch_bytes(s->dev, n, N);
         if (need > s->scratch_bytes)
             return fail(TEXIR_ERR_INVALID, "texir_irt_generate: the stream is being captured and the launch needs %zu bytes of scratch, %zu reserved -- call "
@@ -426,27 +492,31 @@ int texir_irt_kernel_name(const texir_scene* s, int64_t n_ids, int32_t N, char* 
     return TEXIR_OK;
 }
 
+// texir_spec_forward and its training form, which also keeps d w_i / d roughness (dw_ws) and so always needs the Ls_ws workspace
+static int spec_forward_call(const char* fn, bool train, const texir_scene* s, const float* normal, const float* albedo, const float* rough, const float* points,
+                             const float* irr, const float* cam, const float* shift, int64_t P, int32_t S, float clamp_eps, int32_t ls_given, float* rgb, float* Ls_ws,
+                             float* dw_ws, void* stream)
+{
+    if ((!s && !ls_given) || !normal || !albedo || !rough || !points || !irr || !cam || !shift || !rgb || (train && (!Ls_ws || !dw_ws)))
+        return fail(TEXIR_ERR_INVALID, "%s: null argument", fn);
+    if (ls_given && !Ls_ws) return fail(TEXIR_ERR_INVALID, "%s: ls_given needs the lighting in Ls_ws", fn);
+    if (P < 0 || S <= 0 || !(clamp_eps > 0.f)) return fail(TEXIR_ERR_INVALID, "%s: bad sizes P=%lld S=%d clamp_eps=%g", fn, (long long)P, S, (double)clamp_eps);
+    SceneDev none{};
+    HIP_TRY(launch_spec_fwd(s ? dev_of(s) : none, normal, albedo, rough, points, irr, cam, shift, P, S, clamp_eps, ls_given ? 1 : 0, rgb, Ls_ws, (hipStream_t)stream, dw_ws));
+    return TEXIR_OK;
+}
+
 int texir_spec_forward(const texir_scene* s, const float* normal, const float* albedo, const float* rough, const float* points, const float* irr,
                        const float* cam, const float* shift, int64_t P, int32_t S, float clamp_eps, int32_t ls_given, float* rgb, float* Ls_ws, void* stream)
 {
-    if ((!s && !ls_given) || !normal || !albedo || !rough || !points || !irr || !cam || !shift || !rgb) return fail(TEXIR_ERR_INVALID, "texir_spec_forward: null argument");
-    if (ls_given && !Ls_ws) return fail(TEXIR_ERR_INVALID, "texir_spec_forward: ls_given needs the lighting in Ls_ws");
-    if (P < 0 || S <= 0 || !(clamp_eps > 0.f)) return fail(TEXIR_ERR_INVALID, "texir_spec_forward: bad sizes P=%lld S=%d clamp_eps=%g", (long long)P, S, (double)clamp_eps);
-    SceneDev none{};
-    HIP_TRY(launch_spec_fwd(s ? dev_of(s) : none, normal, albedo, rough, points, irr, cam, shift, P, S, clamp_eps, ls_given ? 1 : 0, rgb, Ls_ws, (hipStream_t)stream));
-    return TEXIR_OK;
+    return spec_forward_call("texir_spec_forward", false, s, normal, albedo, rough, points, irr, cam, shift, P, S, clamp_eps, ls_given, rgb, Ls_ws, nullptr, stream);
 }
 
 int texir_spec_forward_train(const texir_scene* s, const float* normal, const float* albedo, const float* rough, const float* points, const float* irr,
                              const float* cam, const float* shift, int64_t P, int32_t S, float clamp_eps, int32_t ls_given, float* rgb, float* Ls_ws, float* dw_ws,
                              void* stream)
 {
-    if ((!s && !ls_given) || !normal || !albedo || !rough || !points || !irr || !cam || !shift || !rgb || !Ls_ws || !dw_ws)
-        return fail(TEXIR_ERR_INVALID, "texir_spec_forward_train: null argument");
-    if (P < 0 || S <= 0 || !(clamp_eps > 0.f)) return fail(TEXIR_ERR_INVALID, "texir_spec_forward_train: bad sizes P=%lld S=%d clamp_eps=%g", (long long)P, S, (double)clamp_eps);
-    SceneDev none{};
-    HIP_TRY(launch_spec_fwd(s ? dev_of(s) : none, normal, albedo, rough, points, irr, cam, shift, P, S, clamp_eps, ls_given ? 1 : 0, rgb, Ls_ws, (hipStream_t)stream, dw_ws));
-    return TEXIR_OK;
+    return spec_forward_call("texir_spec_forward_train", true, s, normal, albedo, rough, points, irr, cam, shift, P, S, clamp_eps, ls_given, rgb, Ls_ws, dw_ws, stream);
 }
 
 int texir_spec_backward_ws(const float* irr, const float* Ls_ws, const float* dw_ws, const float* d_rgb, int64_t P, int32_t S, float* d_albedo, float* d_rough, void* stream)
@@ -472,7 +542,7 @@ int texir_diffuse_irradiance(const texir_scene* s, const float* pos, const float
     if (!s || !pos || !nrm || !shift || !irr) return fail(TEXIR_ERR_INVALID, "texir_diffuse_irradiance: null argument");
     if (sample_type < 0 || sample_type > 1) return fail(TEXIR_ERR_INVALID, "texir_diffuse_irradiance: sample_type must be uniform(0) or cosine(1)");
     if (N <= 0 || P < 0 || P >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "texir_diffuse_irradiance: bad sizes N=%d P=%lld", N, (long long)P);
-    unsigned long long* work = s->d_work + (size_t)(s->work_next.fetch_add(1) % texir_scene::kWorkSlots) * 8 * kWorkStride;
+    unsigned long long* work = next_work_slot(s);
     // uniform: (2 pi / N) sum L n.l -- the IrT estimator; cosine: (pi / N) sum L over cosine-distributed directions
     const int mode = sample_type == 1 ? (1 | 4) : 0;
     HIP_TRY(launch_irt(dev_of(s), pos, nrm, shift, nullptr, P, N, mode, irr, nullptr, work, (hipStream_t)stream));
@@ -509,18 +579,11 @@ int texir_gbuffer_cast(const texir_scene* s, const float* mvp, int32_t c, int32_
 int32_t texir_mip_levels(int32_t H, int32_t W, int32_t max_mip_level) { return mip_levels(H, W, max_mip_level); }
 int64_t texir_mip_elems(int32_t H, int32_t W, int32_t C, int32_t levels) { return mip_total_elems(H, W, C, levels); }
 
-static int check_tex(const char* fn, int H, int W, int C, int levels)
-{
-    if (H <= 0 || W <= 0 || C <= 0 || C > 4 || levels < 1 || levels > 16) return fail(TEXIR_ERR_INVALID, "%s: bad texture H=%d W=%d C=%d levels=%d", fn, H, W, C, levels);
-    if (levels > mip_levels(H, W, 15)) return fail(TEXIR_ERR_INVALID, "%s: %d mip levels not available for %dx%d", fn, levels, H, W);
-    return 0;
-}
-
 int texir_mip_build(const float* tex, float* mips_rest, int32_t H, int32_t W, int32_t C, int32_t levels, int32_t from_level, void* stream)
 {
     if (!tex || !mips_rest) return fail(TEXIR_ERR_INVALID, "texir_mip_build: null argument");
     if (from_level < 0 || from_level > 1) return fail(TEXIR_ERR_INVALID, "texir_mip_build: from_level must be 0 or 1");
-    if (int rc = check_tex("texir_mip_build", H, W, C, levels)) return rc;
+    if (int rc = check_tex("texir_mip_build", -1, H, W, C, levels)) return rc;
     HIP_TRY(launch_mip_build(tex, mips_rest, H, W, C, levels, from_level, (hipStream_t)stream));
     return TEXIR_OK;
 }
@@ -528,10 +591,9 @@ int texir_mip_build(const float* tex, float* mips_rest, int32_t H, int32_t W, in
 int texir_tex_fetch_forward(const float* tex, const float* mips_rest, int32_t H, int32_t W, int32_t C, int32_t levels, const float* uv,
                             const float* uv_da, int32_t filter_mode, int64_t P, float* out, void* stream)
 {
-    if (!tex || !uv || !out || (filter_mode == 1 && (!uv_da || (levels > 1 && !mips_rest)))) return fail(TEXIR_ERR_INVALID, "texir_tex_fetch_forward: null argument");
-    if (filter_mode < 0 || filter_mode > 1 || P < 0) return fail(TEXIR_ERR_INVALID, "texir_tex_fetch_forward: bad filter_mode/P");
-    if (int rc = check_tex("texir_tex_fetch_forward", H, W, C, levels)) return rc;
-    HIP_TRY(launch_tex_fetch(tex, mips_rest, H, W, C, levels, uv, uv_da, filter_mode, P, out, (hipStream_t)stream));
+    const texir_tex_fetch_job q = {tex, const_cast<float*>(mips_rest), H, W, C, levels, /*build_from*/ -1, filter_mode, uv, uv_da, P, out};
+    if (int rc = check_fetch_job("texir_tex_fetch_forward", -1, q)) return rc;
+    HIP_TRY(launch_tex_fetch(q, (hipStream_t)stream));
     return TEXIR_OK;
 }
 
@@ -540,7 +602,7 @@ int texir_tex_fetch_backward(float* d_tex, float* grad_rest, int32_t H, int32_t 
 {
     if (!d_tex || !uv || !d_out || (filter_mode == 1 && (!uv_da || (levels > 1 && !grad_rest)))) return fail(TEXIR_ERR_INVALID, "texir_tex_fetch_backward: null argument");
     if (filter_mode < 0 || filter_mode > 1 || P < 0) return fail(TEXIR_ERR_INVALID, "texir_tex_fetch_backward: bad filter_mode/P");
-    if (int rc = check_tex("texir_tex_fetch_backward", H, W, C, levels)) return rc;
+    if (int rc = check_tex("texir_tex_fetch_backward", -1, H, W, C, levels)) return rc;
     HIP_TRY(launch_tex_fetch_bwd(d_tex, grad_rest, H, W, C, levels, uv, uv_da, filter_mode, P, d_out, 0, (hipStream_t)stream));
     return TEXIR_OK;
 }
@@ -550,7 +612,7 @@ int texir_tex_fetch_backward_deferred(float* d_tex, float* grad_rest, int32_t H,
 {
     if (!d_tex || !uv || !d_out || !uv_da || !grad_rest) return fail(TEXIR_ERR_INVALID, "texir_tex_fetch_backward_deferred: null argument");
     if (P < 0 || levels < 2) return fail(TEXIR_ERR_INVALID, "texir_tex_fetch_backward_deferred: needs P >= 0 and at least two mip levels");
-    if (int rc = check_tex("texir_tex_fetch_backward_deferred", H, W, C, levels)) return rc;
+    if (int rc = check_tex("texir_tex_fetch_backward_deferred", -1, H, W, C, levels)) return rc;
     HIP_TRY(launch_tex_fetch_bwd(d_tex, grad_rest, H, W, C, levels, uv, uv_da, 1, P, d_out, 1, (hipStream_t)stream));
     return TEXIR_OK;
 }
@@ -560,7 +622,7 @@ int texir_tex_taps(int32_t H, int32_t W, int32_t C, int32_t levels, const float*
 {
     if (!uv || !keys || !weights || (filter_mode == 1 && !uv_da)) return fail(TEXIR_ERR_INVALID, "texir_tex_taps: null argument");
     if (filter_mode < 0 || filter_mode > 1 || P < 0) return fail(TEXIR_ERR_INVALID, "texir_tex_taps: bad filter_mode/P");
-    if (int rc = check_tex("texir_tex_taps", H, W, C, levels)) return rc;
+    if (int rc = check_tex("texir_tex_taps", -1, H, W, C, levels)) return rc;
     HIP_TRY(launch_tex_taps(H, W, C, levels, uv, uv_da, filter_mode, P, (long long*)keys, weights, (hipStream_t)stream));
     return TEXIR_OK;
 }
@@ -569,16 +631,10 @@ int texir_tex_gather_backward(float* d_tex, float* grad_rest, int32_t H, int32_t
                               const int32_t* seg_start, const int32_t* seg_count, int32_t n_seg, const int32_t* pix, const float* weights,
                               const float* d_out, int32_t filter_mode, int32_t defer_last_fold, void* stream)
 {
-    // d_tex may be NULL with defer_last_fold when no tap of the lists samples level 0 (then nothing is written there and the caller's
-    // optimiser step treats the level-0 gradient as identically zero)
-    if ((!d_tex && !defer_last_fold) || !d_out || (n_seg > 0 && (!seg_key || !seg_start || !seg_count || !pix || !weights)) || (filter_mode == 1 && levels > 1 && !grad_rest))
-        return fail(TEXIR_ERR_INVALID, "texir_tex_gather_backward: null argument");
-    if (filter_mode < 0 || filter_mode > 1 || n_seg < 0 || defer_last_fold < 0 || defer_last_fold > 2 || (defer_last_fold && (filter_mode != 1 || levels < 2))
-        || (defer_last_fold == 2 && (levels < 4 || (H & 3) || (W & 3))))
-        return fail(TEXIR_ERR_INVALID, "texir_tex_gather_backward: bad filter_mode/n_seg/defer_last_fold");
-    if (int rc = check_tex("texir_tex_gather_backward", H, W, C, levels)) return rc;
-    HIP_TRY(launch_tex_gather_bwd(d_tex, grad_rest, H, W, C, levels, (const long long*)seg_key, seg_start, seg_count, n_seg, pix, weights, d_out,
-                                  filter_mode, defer_last_fold, (hipStream_t)stream));
+    const texir_tex_gather_job q = {d_tex, grad_rest, H, W, C, levels, seg_key, seg_start, seg_count, n_seg, pix, weights, d_out, filter_mode, defer_last_fold,
+                                    /*rest_mask*/ nullptr, /*d_out2*/ nullptr};
+    if (int rc = check_gather_job("texir_tex_gather_backward", -1, q)) return rc;
+    HIP_TRY(launch_tex_gather_bwd(q, (hipStream_t)stream));
     return TEXIR_OK;
 }
 
@@ -586,10 +642,10 @@ int texir_adam_step_tex(float* param, const float* grad, const uint32_t* grad_ma
                         float* exp_avg_sq, float* mip_level1, int32_t H, int32_t W, int32_t C, float lr, float beta1, float beta2, float eps, int32_t step,
                         float clamp_lo, float clamp_hi, void* stream)
 {
-    if (!param || !grad_level1 || !exp_avg || !exp_avg_sq) return fail(TEXIR_ERR_INVALID, "texir_adam_step_tex: null argument");
-    if (H < 2 || W < 2 || (H & 1) || (W & 1) || C < 1 || C > 4 || step < 1) return fail(TEXIR_ERR_INVALID, "texir_adam_step_tex: bad H/W/C/step");
-    if (grad_level2 && ((H & 3) || (W & 3))) return fail(TEXIR_ERR_INVALID, "texir_adam_step_tex: a level-2 gradient needs H and W divisible by 4");
-    HIP_TRY(launch_adam_tex(param, grad, grad_mask, grad_level1, grad_level2, exp_avg, exp_avg_sq, mip_level1, H, W, C, lr, beta1, beta2, eps, step, clamp_lo, clamp_hi, nullptr, (hipStream_t)stream));
+    const texir_adam_tex_job q = {param, grad, grad_mask, grad_level1, /*level1_mask*/ nullptr, grad_level2, exp_avg, exp_avg_sq, mip_level1, H, W, C, /*hyper*/ nullptr,
+                                  beta1, beta2, eps, clamp_lo, clamp_hi};
+    if (int rc = check_adam_tex_job("texir_adam_step_tex", -1, q, &step)) return rc;
+    HIP_TRY(launch_adam_tex(q, lr, step, (hipStream_t)stream));
     return TEXIR_OK;
 }
 
@@ -623,12 +679,39 @@ int texir_adam_step_tex_dev(float* param, const float* grad, const uint32_t* gra
                             float* exp_avg_sq, float* mip_level1, int32_t H, int32_t W, int32_t C, const float* hyper, float beta1, float beta2, float eps,
                             float clamp_lo, float clamp_hi, void* stream)
 {
-    if (!param || (!grad_level1 && !grad_level2) || !exp_avg || !exp_avg_sq || !hyper) return fail(TEXIR_ERR_INVALID, "texir_adam_step_tex_dev: null argument");
-    if (H < 2 || W < 2 || (H & 1) || (W & 1) || C < 1 || C > 4) return fail(TEXIR_ERR_INVALID, "texir_adam_step_tex_dev: bad H/W/C");
-    if (grad_level2 && ((H & 3) || (W & 3))) return fail(TEXIR_ERR_INVALID, "texir_adam_step_tex_dev: a level-2 gradient needs H and W divisible by 4");
-    HIP_TRY(launch_adam_tex(param, grad, grad_mask, grad_level1, grad_level2, exp_avg, exp_avg_sq, mip_level1, H, W, C, 0.f, beta1, beta2, eps, 1, clamp_lo, clamp_hi, hyper,
-                            (hipStream_t)stream));
+    const texir_adam_tex_job q = {param, grad, grad_mask, grad_level1, /*level1_mask*/ nullptr, grad_level2, exp_avg, exp_avg_sq, mip_level1, H, W, C, hyper,
+                                  beta1, beta2, eps, clamp_lo, clamp_hi};
+    if (int rc = check_adam_tex_job("texir_adam_step_tex_dev", -1, q)) return rc;
+    HIP_TRY(launch_adam_tex(q, 0.f, 1, (hipStream_t)stream));
     return TEXIR_OK;
+}
+
+/* ---- the batched forms: every job is held to the rules of its single-texture call, then one launch per kind of kernel (material.hip, adam.hip) ---- */
+const char* texir_batch_last_error(void) { return texir_last_error(); }
+
+int texir_grad_add_masked(float* g, const float* g0, const uint32_t* mask, int64_t n_texels, int32_t C, void* stream)
+{
+    if (n_texels < 0 || C < 1 || C > 4) return fail(TEXIR_ERR_INVALID, "texir_grad_add_masked: bad size n_texels=%lld C=%d", (long long)n_texels, (int)C);
+    if (n_texels == 0) return TEXIR_OK;
+    if (!g || !g0 || !mask) return fail(TEXIR_ERR_INVALID, "texir_grad_add_masked: null argument");
+    HIP_TRY(launch_grad_add_masked(g, g0, mask, n_texels, C, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
+int texir_tex_fetch_forward_batch(const texir_tex_fetch_job* jobs, int32_t n, void* stream)
+{
+    return batch_call("texir_tex_fetch_forward_batch", jobs, n, stream, check_fetch_job, launch_tex_fetch_batch);
+}
+
+int texir_tex_gather_backward_batch(const texir_tex_gather_job* jobs, int32_t n, void* stream)
+{
+    return batch_call("texir_tex_gather_backward_batch", jobs, n, stream, check_gather_job, launch_tex_gather_bwd_batch);
+}
+
+int texir_adam_step_tex_dev_batch(const texir_adam_tex_job* jobs, int32_t n, void* stream)
+{
+    auto check = [](const char* fn, int k, const texir_adam_tex_job& q) { return check_adam_tex_job(fn, k, q); };
+    return batch_call("texir_adam_step_tex_dev_batch", jobs, n, stream, check, launch_adam_tex_batch);
 }
 
 int64_t texir_loss_workspace_bytes(int64_t P, int32_t C, int32_t R) { return (int64_t)loss_workspace_bytes(P, C, R); }

@@ -34,7 +34,7 @@ constexpr int kSentinel = 0x7FFFFFFF;
 constexpr int kStackCap = 96;        // LDS part + private overflow; the host checks the tree's worst case against it
 
 // ------------------------------------------------------------------------------------------------
-// build configuration of the traversal, shared by every tracing kernel (kernels.hip, material.hip, texbake.hip, irtsplit.hip, irtlight.hip)
+// build configuration of the traversal, shared by every tracing kernel (kernels.hip, gbuffer.hip, texbake.hip, irtsplit.hip, irtlight.hip)
 // ------------------------------------------------------------------------------------------------
 // Occupancy.  Round 1 (4-byte stack entries): 5 waves / 24 entries 13.85, 6 / 24 14.79, 7 / 16 15.11, 8 / 16 15.06 Grays/s (c4).  Round 2, after the
 // scalar node path took the L1 off the critical path (8-byte entries): 6 waves / 12 entries 15.01, 7 / 11 15.82, 8 / 10 15.87 (c2: 16.30, 17.11, 17.40;

@@ -43,21 +43,21 @@ hipError_t launch_gbuffer(const SceneDev& sc, const float* mvp_host, const float
 int mip_levels(int H, int W, int max_mip_level);
 int64_t mip_total_elems(int H, int W, int C, int levels);
 hipError_t launch_mip_build(const float* tex, float* rest, int H, int W, int C, int levels, int from_level, hipStream_t st);
-hipError_t launch_tex_fetch(const float* tex, const float* rest, int H, int W, int C, int levels, const float* uv, const float* uvda, int trilinear,
-                            int64_t P, float* out, hipStream_t st);
 hipError_t launch_tex_fetch_bwd(float* d_tex, float* grad_rest, int H, int W, int C, int levels, const float* uv, const float* uvda, int trilinear,
                                 int64_t P, const float* d_out, int fold_to_level, hipStream_t st);
 hipError_t launch_tex_taps(int H, int W, int C, int levels, const float* uv, const float* uvda, int trilinear, int64_t P, long long* keys,
                            float* weights, hipStream_t st);
-hipError_t launch_tex_gather_bwd(float* d_tex, float* grad_rest, int H, int W, int C, int levels, const long long* seg_key, const int* seg_start,
-                                 const int* seg_count, int n_seg, const int* pix, const float* w, const float* d_out, int trilinear,
-                                 int fold_to_level, hipStream_t st);
-hipError_t launch_adam_tex(float* p, const float* g /*nullable*/, const uint32_t* l0_mask /*nullable*/, const float* g1, const float* g2 /*nullable*/, float* m, float* v, float* mip1 /*nullable*/,
-                           int H, int W, int C, float lr,
-                           float beta1, float beta2, float eps, int step, float lo, float hi, const float* hyper /*dev, nullable: step size + bias correction*/, hipStream_t st);
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int step,
                        float lo, float hi, const float* hyper /*dev, nullable*/, hipStream_t st);
 hipError_t launch_adam_tick(double* state, float* hyper, int n, unsigned long long mask, hipStream_t st);
+// on the job structures of include/texir_hip.h (validated): one texture, then the batched forms -- n >= 1 jobs, one launch per kind of kernel
+hipError_t launch_tex_fetch(const texir_tex_fetch_job& q, hipStream_t st);
+hipError_t launch_tex_gather_bwd(const texir_tex_gather_job& q, hipStream_t st);
+hipError_t launch_adam_tex(const texir_adam_tex_job& q, float lr /*lr, step: used when q.hyper is null*/, int step, hipStream_t st);
+hipError_t launch_tex_fetch_batch(const texir_tex_fetch_job* jobs, int n, hipStream_t st);
+hipError_t launch_tex_gather_bwd_batch(const texir_tex_gather_job* jobs, int n, hipStream_t st);
+hipError_t launch_adam_tex_batch(const texir_adam_tex_job* jobs, int n, hipStream_t st);
+hipError_t launch_grad_add_masked(float* g, const float* g0, const uint32_t* mask, int64_t n_texels, int C, hipStream_t st);
 // texpost.hip: the pad + denoise step between the two stages (tools/padding_texture.py:49-87)
 size_t texpost_pad_workspace_bytes(int H, int W);
 hipError_t launch_texture_pad(const float* img, int H, int W, int C, const int32_t* row_map, const int32_t* col_map, float* out, int32_t* src, void* workspace,

@@ -1,7 +1,11 @@
-// Host-side helpers the launchers share: grid sizes and the parts-per-texel rule of the 64-texel IrT plan.
+// Helpers the launchers share: grid sizes, the channel-count dispatch, the block ranges of a batched launch and the parts-per-texel rule of the 64-texel IrT plan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
+
+#include "../../include/texir_hip.h"
 
 namespace texir {
 
@@ -10,6 +14,31 @@ inline int grid_capped(int64_t per_block, int64_t n, int64_t cap = 2048)
 {
     const int64_t want = (n + per_block - 1) / per_block;
     return (int)(want < 1 ? 1 : (want > cap ? cap : want));
+}
+
+// f(std::integral_constant<int, C>{}) for a texture's run-time channel count C in 1..4 (validated by the caller): the kernels take it at compile time.
+// On the host it picks the instantiation to launch, in the batched kernels the body of the block's job.
+template <class F>
+__host__ __device__ __forceinline__ void with_channels(int C, F&& f)
+{
+    switch (C) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+
+// batched launches (material.hip, adam.hip): a batch structure is { int n; Job j[kMaxBatch]; }, and its jobs own consecutive block ranges [first, next job's first)
+constexpr int kMaxBatch = TEXIR_MAX_BATCH;
+
+template <class B>
+__device__ __forceinline__ int job_of_block(const B& b, int bid)
+{
+    int k = 0;
+#pragma unroll
+    for (int i = 1; i < kMaxBatch; i++) if (i < b.n && bid >= b.j[i].first) k = i;
+    return k;
 }
 
 // workgroups that are co-resident on the whole chip for a kernel (so a grid-stride loop has no second, partial round)

@@ -3,7 +3,7 @@ usage: python tools/mat_step_pmc.py <dir with mat_rd.csv / mat_wr.csv / mat_tcc.
 import collections, csv, hashlib, json, os, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAT_SOURCES = ["material.hip", "loss.hip", "kernels.hip", "device_common.h", "kernels.h", "capi.hip", "Makefile"]
+MAT_SOURCES = ["gbuffer.hip", "material.hip", "adam.hip", "launch_util.h", "loss.hip", "kernels.hip", "device_common.h", "kernels.h", "capi.hip", "Makefile"]
 
 
 def mat_src_sha():
