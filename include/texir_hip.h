@@ -666,6 +666,101 @@ TEXIR_API int texir_irt_lights_any(const texir_scene* scene, const float* pos /*
                        const int32_t* texel_ids /*dev, nullable = all Nt*/, int64_t n_ids, int64_t Nt, const float* lights /*dev [K][16]*/, int32_t K /*0..8*/,
                        int32_t S /*1..65536*/, float t_max, float* F /*dev [K][Nt]*/, uint64_t* stats /*dev [2], nullable*/, void* stream);
 
+/* ---- inserted emitters: the SPECULAR response to new area lights per pixel (csrc/speclight.hip).  texir_irt_lights gives the factor F of the diffuse
+ * response; a view relit by new lamps is  rgb + sum_k colour_k (albedo / pi F[k] + R[k]),  and this call gives R.  The material model's Fresnel term is
+ * the scalar 0.04 + 0.96 2^(..), so the GGX response to a light of radiance colour_k is colour_k times a SCALAR per-pixel factor.  The light is neither
+ * in the mesh nor in the radiance texture, so texir_spec_forward cannot see it.  Sampling the lobe alone misses a small lamp from a rough surface,
+ * sampling the light's area alone aliases on a glossy one: the estimate combines the two by the balance heuristic (Veach), both techniques at the SAME
+ * Hammersley point.  Direct light only: no bounce of the new light.  The reference has no counterpart (tools/relighting_varying.py leaves the scene to an
+ * external renderer).
+ *
+ * THE RULE.  Per pixel p: x = pos (already offset by the caller), n = nrm (RAW), r = rough, the pixel's Cranley-Patterson shift (the one
+ * texir_spec_forward takes), the camera c (3 floats in DEVICE memory).  v = (c - x) / max(|c - x|, 1e-4);  the frame (nh, U, V) = make_frame(n) of
+ * texir_generate_dir, nh = n / (|n| + 1e-6).  Light records: the 16-float DEVICE records of texir_irt_lights, same layout, same validation; a record
+ * that rule refuses yields R = 0 for that light, and no ray is traced for it.
+ *   For sample i = 0 .. S-1:  (s0, s1) as in texir_irt_lights, the same point for both techniques.
+ *   LIGHT SAMPLE  y, m, w, d = y - x, dd, nd, md exactly as texir_irt_lights has them.  Dead (term 0, no ray) unless nd > 0, md > 0, dd > 0.
+ *                 lh = d / sqrt(dd);  h = (v + lh) / |v + lh|, dead when |v + lh|^2 is not > 0.
+ *                 vdh, ndl, ndh, ndv, Fresnel, k = (r + 1)^2 / 8, G and brdf = Fr G / max(4 ndl ndv, ceps) as texir_spec_forward has them: the dots with
+ *                 the RAW n, clamped to [0, 1].
+ *                 D = a2 / (pi den^2),  a2 = r^4,  den = a2 c^2 + s2,  c = nh . h,  s2 = |nh x h|^2;  D = 0 when c <= 0.  The frame's nh, because that is
+ *                 the density generate_dir samples; the cross-product form, because c^2 (a2 - 1) + 1 loses every digit at r = 0.01 near the peak.
+ *                 pL = dd sqrt(dd) / (w md)  (solid-angle density of the area sample; the quad's m carries its area, w = 1)
+ *                 pB = D c / max(4 vdh, ceps)  (solid-angle density of the lobe sample), but pB = 0 in the lobe's CORE, s2 < (1 - ctmax^2) (nh . nh) with
+ *                 ctmax = 1 - 1e-6 (on sin^2: cos^2 next to 1 has no digits left): generate_dir clamps cos(theta_h) to ctmax, so half vectors within 1.4e-3 rad of nh are never sampled (their mass
+ *                 lands on the rim, where it is no density).  At r = 0.01 that is 99.5 % of the lobe: without this the estimate loses it.
+ *                 term = (D brdf ndl) / (pL + pB)
+ *   LOBE SAMPLE   Dead when the chain's cos(theta_h) = sqrt((1 - s0) / (1 + (a2 - 1) s0)) exceeds ctmax BEFORE its clamp: a rim sample, no draw from a
+ *                 density (texir_spec_forward counts it; this estimate leaves the core to the light samples, so that it converges to the GGX integral).
+ *                 The condition is taken cleared of root and quotient, (1 - s0) (1 - ctmax^2) > ctmax^2 a2 s0: float32 keeps its digits in this form,
+ *                 while the chain's own comparison is within rounding of its edge for every s0 near the rim.
+ *                 l, its weight wv = brdf ndl 4 vdh / max(ndh, ceps), the sampled h and the clamped vdh from the operations of texir_spec_forward.
+ *                 Dead unless wv > 0.  The ray (x, l) meets light k analytically:
+ *                 quad    ml = m . l;  e = o - x;  tL = (m . e) / ml;  d = tL l;  q = d - e;  u = q . ua,  v' = q . vb  with the reciprocal basis
+ *                         ua = (b x m) / (m . m),  vb = (m x a) / (m . m);  hit iff -ml > 0, tL > 0, 0 <= u <= 1, 0 <= v' <= 1.
+ *                 sphere  e = c - x;  b = l . e;  ll = l . l;  cc = e . e - r_s^2;  disc = b b - ll cc;  hit iff cc > 0 (x outside), b > 0, disc >= 0 and
+ *                         tL = cc / (b + sqrt(disc)) > 0  (the nearer root, without the cancellation of b - sqrt(disc));  d = tL l;  m = (d - e) / r_s.
+ *                 dd = d . d,  md = -(m . d);  dead unless md > 0, dd > 0.  pL as above, D and c at the SAMPLED h, pB = D c / max(4 vdh, ceps).
+ *                 term = (wv pB) / (pL + pB)
+ *   A term that is not finite or not > 0 is 0.  A ray is traced iff the term is > 0.
+ *   VISIBILITY    the question of texir_irt_lights for the segment (x, d): V = 0 iff the closest hit has t < t_max.  scene.Scene.spec_lights defaults to 0.999.
+ *   RESULT        acc = for ascending i: the light sample's V term, then the lobe sample's V term, in ONE float32 accumulator;  R[k][p] = acc / float(S).
+ *   WRITES        every LISTED pixel is written for every k, zeros included.  Unlisted pixels are untouched.  An id outside [0, P) is not a pixel.
+ * R is a pure function of the inputs: no atomics on results, no workspace; list order, duplicates, launch shape and stream do not change a bit.
+ *
+ * FLOAT32 OPERATION SEQUENCE (each operation separately rounded, no contraction; sqrt and / correctly rounded; pi32 = 3.14159274, tau32 and fourpi32 of
+ * texir_irt_lights; clamp01(t) = min(max(t, 0), 1)).  y, m, w, d, dd, nd, md: the sequence of texir_irt_lights.  l, wv, h, vdh of the lobe sample: the
+ * sequence of texir_spec_forward's sample chain (csrc/spec_sample.h), value part.
+ *     pixel:   v_i = c_i - x_i;  lv = max(sqrt((v_x v_x + v_y v_y) + v_z v_z), 1e-4);  v_i = v_i / lv;  a1 = r * r;  a2 = a1 * a1
+ *              ctmax = 1 - 1e-6 (float32: 1 - 17 * 2^-24);  core_s2 = 2.02655690e-6 * ((nh_x nh_x + nh_y nh_y) + nh_z nh_z)   (the constant: 1 - ctmax^2)
+ *              ndv = clamp01((n_x v_x + n_y v_y) + n_z v_z);  r1 = r + 1;  k = (r1 * r1) * 0.125;  omk = 1 - k;  g1v = ndv / max(omk * ndv + k, ceps)
+ *     record:  quad: mm = (m_x m_x + m_y m_y) + m_z m_z;  ua_x = (b_y * m_z - b_z * m_y) / mm, ..;  vb_x = (m_y * a_z - m_z * a_y) / mm, ..   (cyclic)
+ *              e_i = p_i - x_i  (p = the record's point o or c);  sphere: rr2 = r_s * r_s
+ *     D(h):    c = (nh_x h_x + nh_y h_y) + nh_z h_z;  q_x = nh_y * h_z - nh_z * h_y, ..;  s2 = (q_x q_x + q_y q_y) + q_z q_z;  den = a2 * (c * c) + s2
+ *              D = a2 / ((pi32 * den) * den)
+ *     light:   ls = sqrt(dd);  lh_i = d_i / ls;  h_i = v_i + lh_i;  hh = (h_x h_x + h_y h_y) + h_z h_z;  hl = sqrt(hh);  h_i = h_i / hl
+ *              vdh = clamp01((h_x v_x + h_y v_y) + h_z v_z);  ndl = clamp01((lh_x n_x + lh_y n_y) + lh_z n_z)
+ *              e = ((vdh * -5.55472) - 6.98316) * vdh;  fr = 0.04 + 0.96 * exp2f(e);  g1l = ndl / max(ndl * omk + k, ceps)
+ *              brdf = (fr * (g1l * g1v)) / max(ndl * (4 * ndv), ceps);  pL = (dd * ls) / (w * md);  pB = s2 < core_s2 ? 0 : (D * c) / max(4 * vdh, ceps)
+ *              term = ((D * brdf) * ndl) / (pL + pB)
+ *     lobe:    dead when (1 - s0) * 2.02655690e-6 > ((ctmax * ctmax) * a2) * s0
+ *              quad:   ml = (m_x l_x + m_y l_y) + m_z l_z;  me = (m_x e_x + m_y e_y) + m_z e_z;  tL = me / ml;  d_i = tL * l_i;  q_i = d_i - e_i
+ *                      u = (q_x ua_x + q_y ua_y) + q_z ua_z;  v' alike with vb
+ *              sphere: b = (l_x e_x + l_y e_y) + l_z e_z;  ll = (l_x l_x + l_y l_y) + l_z l_z;  cc = ((e_x e_x + e_y e_y) + e_z e_z) - rr2
+ *                      disc = b * b - ll * cc;  tL = cc / (b + sqrt(disc));  d_i = tL * l_i;  m_i = (d_i - e_i) / r_s
+ *              dd = (d_x d_x + d_y d_y) + d_z d_z;  md = -((m_x d_x + m_y d_y) + m_z d_z);  pL = (dd * sqrt(dd)) / (w * md);  pB as above
+ *              term = (wv * pB) / (pL + pB)
+ *     acc = acc + term  (visible terms; per i the light sample's, then the lobe sample's);   R = acc / float(S)
+ * ROUNDING BOUND (first order, u = 2^-24; the inputs x, n, r, c, the record, s0, s1 are exact float32 values; the tests multiply every bound by their
+ * factor K).  Number the rounded operations of the sequence above that feed a quantity y -- every sum, product, quotient, sqrt, every constant float32 has
+ * to round, sinf, cosf, exp2f -- j = 1 .. J, with exact results x_j.  Replace x_j by x_j (1 + e_j).  To first order
+ *     |dy| <= sum_j |dy / de_j| (u + 2^-126 / |x_j|)
+ * (one rounding, or one flushed denormal, per operation; scalings by 2, 4, 1/8, negations, selections, min, max and products with 0 or 1 are exact).  This
+ * is a running error bound: it is evaluated AT the operands of the case, so it is as wide as the conditioning there demands and no wider -- the
+ * cross-product form of den keeps it useful at r = 0.01 on the highlight's centre, where the textbook form's bound exceeds the value.  Every decision
+ * above (nd > 0, md > 0, c > 0, the two core tests, -ml > 0, tL > 0, the four edge tests of u and v', cc > 0, b > 0, disc >= 0, the sides of every clamp) is decided unless
+ * the quantity lies within its own bound of the edge; the ray's direction carries the bound of d_i.  A decided live term lies within its bound of its
+ * exact value, a decided dead one is 0, an undecided one lies in [0, value + bound]; a clamp is continuous, so a term with an undecided clamp lies within the
+ * bounds of the values of its two sides.  With T the sum of the terms' upper ends,
+ *     |dR| <= (1 / S) (sum of the terms' bounds + (2 S + 2) u T)                    (2 S - 1 additions, the quotient by S)
+ *
+ *   pos, nrm [P,3], rough [P], shift [P,2] dev;  cam [3] dev;  pixel_ids [n_ids] i32 dev, nullable = all P pixels (n_ids ignored);  lights dev [K][16],
+ *   K in 0..8;  S in 1..65536;  t_max finite;  clamp_eps finite, > 0 (the floor of the denominators: 1e-14 in training, 1e-6 in evaluation);  R dev [K][P].
+ *   stats dev u64[2], nullable: += terms > 0 (the rays traced), and the visible ones; one atomic add per wave and counter.
+ * Errors as texir_irt_lights reports them: K outside 0..8 before any null buffer, S, t_max, negative counts, a null buffer.  K = 0 and an empty list return
+ * 0 and write nothing.  Caller-owned buffers, the caller's stream, no allocation and no synchronisation: the call records into a hipGraph, and the
+ * records and the camera are read again on every replay. */
+TEXIR_API int texir_spec_lights(const texir_scene* scene, const float* pos /*dev [P,3]*/, const float* nrm /*dev [P,3], raw*/, const float* rough /*dev [P]*/,
+                       const float* shift /*dev [P,2]*/, const float* cam /*dev [3]*/, const int32_t* pixel_ids /*dev, nullable = all P*/, int64_t n_ids, int64_t P,
+                       const float* lights /*dev [K][16]*/, int32_t K /*0..8*/, int32_t S /*1..65536*/, float t_max, float clamp_eps, float* R /*dev [K][P]*/,
+                       uint64_t* stats /*dev [2], nullable*/, void* stream);
+/* texir_spec_lights with its VISIBILITY step put as the occlusion query texir_trace_occluded(x, d, 0, t_max).  Same parameters, same errors, same house
+ * rules; it returns the bits of texir_spec_lights, R and stats alike (see texir_irt_lights_any). */
+TEXIR_API int texir_spec_lights_any(const texir_scene* scene, const float* pos /*dev [P,3]*/, const float* nrm /*dev [P,3], raw*/, const float* rough /*dev [P]*/,
+                       const float* shift /*dev [P,2]*/, const float* cam /*dev [3]*/, const int32_t* pixel_ids /*dev, nullable = all P*/, int64_t n_ids, int64_t P,
+                       const float* lights /*dev [K][16]*/, int32_t K /*0..8*/, int32_t S /*1..65536*/, float t_max, float clamp_eps, float* R /*dev [K][P]*/,
+                       uint64_t* stats /*dev [2], nullable*/, void* stream);
+
 /* ---- host-side codec loops of the file formats around the path (both take HOST pointers) ----------------------------
  * PNG scanline un-filtering (filters 0-4, PNG spec 9.2) of zlib-inflated IDAT data: raw [H][stride+1] -> out [H][stride]; replaces the
  * decode half of cv2.imread("0.png", -1) (models/tracer_o3d_irt.py:91, datasets/dataset.py:489-492). */

@@ -26,6 +26,7 @@ def signatures():
     vp, i32, i64, f32, text = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_char_p
     bake = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
     lights = [vp, vp, vp, vp, vp, i64, i64, vp, i32, i32, f32, vp, vp, vp]
+    spec_lights = [vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, i32, i32, f32, f32, vp, vp, vp]
     return {
         "texir_last_error": (text, []),
         "texir_version": [],
@@ -89,6 +90,8 @@ def signatures():
         "texir_atlas_fill": [vp, vp, i64, vp, i64, vp, i64, vp, f32, f32, f32, vp, vp, vp, vp, vp],
         "texir_irt_lights": lights,
         "texir_irt_lights_any": lights,
+        "texir_spec_lights": spec_lights,
+        "texir_spec_lights_any": spec_lights,
         "texir_png_unfilter": [vp, i32, i32, i32, vp],
         "texir_hdr_decode_scanlines": (i64, [vp, i64, i32, i32, vp]),
         "texir_rgbe_encode": [vp, i64, vp],

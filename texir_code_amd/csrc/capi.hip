@@ -906,4 +906,37 @@ int texir_irt_lights_any(const texir_scene* s, const float* pos, const float* nr
     return irt_lights_call("texir_irt_lights_any", true, s, pos, nrm, shift, texel_ids, n_ids, Nt, lights, K, S, t_max, F, stats, stream);
 }
 
+/* ---- inserted emitters, csrc/speclight.hip: the specular response factor R of K new area lights per listed pixel (multiple importance sampling over
+ * the light's area and the GGX lobe; include/texir_hip.h states the rule).  The argument checks and error text are the light pass's ---- */
+static int spec_lights_call(const char* fn, bool any, const texir_scene* s, const float* pos, const float* nrm, const float* rough, const float* shift, const float* cam,
+                            const int32_t* pixel_ids, int64_t n_ids, int64_t P, const float* lights, int32_t K, int32_t S, float t_max, float ceps, float* R,
+                            uint64_t* stats, void* stream)
+{
+    if (K < 0 || K > 8) return fail(TEXIR_ERR_INVALID, "%s: K must be in 0..8, got %d (call again for further lights: the factors add)", fn, K);
+    if (S < 1 || S > 65536) return fail(TEXIR_ERR_INVALID, "%s: S must be in 1..65536, got %d", fn, S);
+    if (!(t_max - t_max == 0.0f)) return fail(TEXIR_ERR_INVALID, "%s: t_max must be finite", fn);
+    if (!(ceps > 0.0f) || !(ceps - ceps == 0.0f)) return fail(TEXIR_ERR_INVALID, "%s: clamp_eps must be finite and > 0 (got %g)", fn, (double)ceps);
+    if (P < 0 || (pixel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "%s: negative pixel count", fn);
+    if (P >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "%s: P too large", fn);
+    const int64_t n = pixel_ids ? n_ids : P;
+    if (K == 0 || n == 0) return TEXIR_OK;
+    if (!s || !pos || !nrm || !rough || !shift || !cam || !lights || !R)
+        return fail(TEXIR_ERR_INVALID, "%s: null argument (scene, pos, nrm, rough, shift, cam, lights and R are required)", fn);
+    HIP_TRY(launch_spec_lights(dev_of(s), pos, nrm, rough, shift, cam, pixel_ids, n, P, lights, K, S, t_max, ceps, R, (unsigned long long*)stats, (hipStream_t)stream, any));
+    return TEXIR_OK;
+}
+
+int texir_spec_lights(const texir_scene* s, const float* pos, const float* nrm, const float* rough, const float* shift, const float* cam, const int32_t* pixel_ids,
+                      int64_t n_ids, int64_t P, const float* lights, int32_t K, int32_t S, float t_max, float clamp_eps, float* R, uint64_t* stats, void* stream)
+{
+    return spec_lights_call("texir_spec_lights", false, s, pos, nrm, rough, shift, cam, pixel_ids, n_ids, P, lights, K, S, t_max, clamp_eps, R, stats, stream);
+}
+
+/* the same factors with visibility as an any-hit query (trace_occluded): the bits of texir_spec_lights */
+int texir_spec_lights_any(const texir_scene* s, const float* pos, const float* nrm, const float* rough, const float* shift, const float* cam, const int32_t* pixel_ids,
+                          int64_t n_ids, int64_t P, const float* lights, int32_t K, int32_t S, float t_max, float clamp_eps, float* R, uint64_t* stats, void* stream)
+{
+    return spec_lights_call("texir_spec_lights_any", true, s, pos, nrm, rough, shift, cam, pixel_ids, n_ids, P, lights, K, S, t_max, clamp_eps, R, stats, stream);
+}
+
 }  // extern "C"

@@ -90,6 +90,10 @@ hipError_t launch_irt_split(const SceneDev& sc, const float* tex_row_major, cons
 hipError_t launch_irt_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt,
                              const float* lights /*dev [K][16]*/, int K, int S, float t_max, float* F /*[K][Nt]*/, unsigned long long* stats /*nullable*/, hipStream_t st,
                              bool any = false);
+// speclight.hip: the specular (GGX) response factors of inserted area lights per listed pixel, balance-heuristic MIS over the light's area and the lobe
+hipError_t launch_spec_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* rough, const float* shift, const float* cam /*dev [3]*/,
+                              const int32_t* ids /*nullable: all P*/, int64_t n, int64_t P, const float* lights /*dev [K][16]*/, int K, int S, float t_max, float ceps,
+                              float* R /*[K][P]*/, unsigned long long* stats /*nullable*/, hipStream_t st, bool any = false);
 // occlusion.hip: is anything in the way inside (t_near, t_far)?  One any-hit query per ray (Open3D RaycastingScene.test_occlusions)
 hipError_t launch_trace_occluded(const SceneDev& sc, const float* org, const float* dir, int64_t R, float t_near, float t_far, uint8_t* occluded,
                                  unsigned long long* stats /*nullable*/, hipStream_t st);

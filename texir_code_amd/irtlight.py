@@ -9,6 +9,7 @@ import numpy as np
 
 MAX_LIGHTS = 8
 QUAD, SPHERE = 0.0, 1.0
+PI32 = float(np.float32(np.pi))              # pi as the kernels have it
 
 
 def _vec3(v, what):
@@ -98,4 +99,19 @@ def add(E, F, colours):
     out = E
     for k in range(F.shape[0]):
         out = out + F[k][..., None] * _colour(colours[k], E)
+    return out
+
+
+def add_view(rgb, albedo, F, R, colours):
+    """a view relit by inserted emitters: rgb + sum_k colours[k] * (albedo / pi * F[k] + R[k]).  rgb, albedo [...,3]; F [K,...] the lights' irradiance
+    factors at the view's pixels (Scene.irt_lights), R [K,...] their specular response factors (Scene.spec_lights); colours [K] scalars or [K,3] -> [...,3].
+    numpy or torch; the terms are added in ascending k"""
+    if len(colours) != F.shape[0] or tuple(R.shape) != tuple(F.shape):
+        raise ValueError("%d colours, F %r, R %r: one colour per light and R shaped as F" % (len(colours), tuple(F.shape), tuple(R.shape)))
+    if tuple(F.shape[1:]) != tuple(rgb.shape[:-1]) or rgb.shape[-1] != 3 or tuple(albedo.shape) != tuple(rgb.shape):
+        raise ValueError("rgb %r, albedo %r and F %r do not match ([...,3], [...,3] and [K,...])" % (tuple(rgb.shape), tuple(albedo.shape), tuple(F.shape)))
+    out = rgb
+    pi = _colour([PI32], rgb)                     # (an array, not a scalar: a torch division by a Python scalar multiplies by its reciprocal)
+    for k in range(F.shape[0]):
+        out = out + (albedo / pi * F[k][..., None] + R[k][..., None]) * _colour(colours[k], rgb)
     return out

@@ -11,7 +11,7 @@ _REGISTRY = {
     "datasets.dataset.ImageCubeDerived": "texir_code_amd.datasets.ImageCubeDerived",
     "datasets.dataset.ImageCubeSyn": "texir_code_amd.datasets.ImageCubeSyn",
     # evaluation re-use: the tester runners' model and datasets
-    "models.test_nvdiffrast.MaterialModel": "texir_code_amd.tester.test_model.MaterialModel",
+    "models.test_nvdiffrast.MaterialModel": "texir_code_amd.tester.lit_model.MaterialModel",        # (test_model.MaterialModel + test.lights)
     "datasets.dataset.ImageCubeNovel": "texir_code_amd.datasets.ImageCubeNovel",
     # NIrF slice
     "models.tracer_o3d_irrf.TracerO3d": "texir_code_amd.nirf.TracerO3dIrrF",

@@ -262,6 +262,42 @@ class Scene:
         return (out, st) if stats else out
 
 
+    # -- the specular response to inserted emitters (include/texir_hip.h texir_spec_lights) -----------------
+    def spec_lights(self, pos, nrm, rough, shift, cam, lights, n_samples, texel_ids=None, t_max=0.999, clamp_eps=1e-14, query="closest", out=None, stats=False):
+        """specular (GGX) response factors of inserted area lights per pixel: pos, nrm [P,3] (pos already offset), rough [P], shift [P,2] (the pixels'
+        specular shift), cam [3], lights [K,16] float32 records (irtlight.pack; a device tensor is used in place, as is a device cam, so a recorded graph
+        replays with whatever they hold then), K <= 8 -> R [K, P]; the radiance a light of colour c_k adds to the view is c_k * R[k] beside its diffuse
+        albedo / pi * c_k * F[k] (irtlight.add_view).  Balance-heuristic multiple importance sampling over the light's area and the GGX lobe, n_samples
+        points each.  t_max, query, stats, out, texel_ids (here: pixel ids): as irt_lights.  clamp_eps: the material model's floor of denominators."""
+        call = "texir_spec_lights_any" if check_query(query) else "texir_spec_lights"
+        pos = _dev_f32(pos, self.device).reshape(-1, 3)
+        nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
+        P = pos.shape[0]
+        rough = _dev_f32(rough, self.device).reshape(P)
+        shift = _dev_f32(shift, self.device).reshape(P, 2)
+        cam = _dev_f32(cam, self.device).reshape(3)
+        lights = _dev_f32(lights, self.device)
+        if lights.ndim != 2 or lights.shape[1] != 16:
+            raise ValueError("lights must be [K,16], got %r" % (tuple(lights.shape),))
+        K = lights.shape[0]
+        if out is None:
+            out = torch.zeros((K, P), device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (K, P) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float32 [%d,%d] on %s" % (K, P, self.device))
+        ids = None
+        n_ids = 0
+        if texel_ids is not None:
+            ids = texel_ids.to(device=self.device, dtype=torch.int32).contiguous()
+            n_ids = ids.numel()
+        st = torch.zeros(2, device=self.device, dtype=torch.int64) if stats else None
+        empty = P == 0 or (texel_ids is not None and n_ids == 0)           # (an EMPTY id list must not reach the library as "no list = all pixels")
+        if not empty:
+            _lib.check(getattr(_lib.lib(), call)(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(rough), _lib.ptr(shift), _lib.ptr(cam), _lib.ptr(ids), n_ids, P,
+                                                 _lib.ptr(lights) if K else None, K, int(n_samples), float(t_max), float(clamp_eps),
+                                                 _lib.ptr(out) if K else None, _lib.ptr(st), _lib.stream_ptr()))
+        return (out, st) if stats else out
+
+
 def generate_dir(normals, num_sample_dir, shift, mode="uniform", roughness=None):
     """utils/sample_util.py:63-146 on the GPU; `shift` [b,2] is the torch.rand(b,1,2) of :102 made explicit."""
     dev = normals.device
