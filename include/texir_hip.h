@@ -194,6 +194,37 @@ TEXIR_API int texir_irt_split(const texir_scene* scene, const float* pos /*dev*/
                        const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode, const uint8_t* labels /*dev [Ht,Wt]*/,
                        int32_t K, int32_t unit, float* out /*dev [K][Nt][3]*/, void* workspace /*dev*/, int64_t workspace_bytes, void* stream);
 
+/* ---- several radiance textures in one traced IrT pass (csrc/irtmulti.hip): the IrT estimator applied to K caller-owned textures instead of the one the
+ * scene holds.  The light a texel throws back under an inserted emitter is a radiance texture of its own (albedo / pi * colour * F, irtlight.bounce_textures);
+ * its irradiance elsewhere is this estimator on that texture -- without set_texture, without a re-tile and without tracing the identical rays once per light.
+ *
+ * THE RULE.  Inputs: everything texir_irt_generate takes; tex dev float32 [Ht][Wt][K][3], the K textures interleaved per texel, Ht x Wt the size and the
+ * orientation of the texture the scene holds (tex[y][x][k] is what the hit shader would read at row y, column x of texture k; as `labels` of
+ * texir_irt_split); K in 1..8.
+ *   SAMPLES AND RAYS  directions, n.l from the raw normal, the ray, the acceptance test (slot >= 0 && t > 1e-4) and the closest hit are exactly those of
+ *               irt_group_kernel<false, 4, 6>, texir_irt_generate's 64-texel form: one texel per lane, one sample per pass.
+ *   SHADING     for a hit, x0, y0, x1, y1, w00, w10, w01, w11 are computed exactly as the hit shader computes them (bilinear / border /
+ *               align_corners=False).  For texture k and channel c, separately rounded float32 operations in this order:
+ *                   L_k[c] = v00 w00;  L_k[c] += v10 w10;  L_k[c] += v01 w01;  L_k[c] += v11 w11,     v_ab = tex[y_b][x_a][k][c]
+ *               No select, no label.  Textures q >= K are not read (the buffer has none); the scene's own texture is not read at all.
+ *   REDUCTION   the 64-texel plan of texir_irt_split under the same switches (TEXIR_IRT_MIN_PART_CELLS, TEXIR_IRT_LOG2PARTS): acc_k += L_k ndl per lane
+ *               over the passes of a part, in irt_group_kernel's pass order; partial[part][k][i][3]; the parts are added in part order;
+ *               out[k][t][c] = ((a * 2) * pi) / N.
+ *   CONSEQUENCE out[k] is, bit for bit, what texir_irt_generate in its 64-texel form (TEXIR_IRT_TEXELS_PER_WAVE=64, or any list of >= 32 768 texels)
+ *               writes for the same scene after texir_scene_set_texture(T_k), whatever layout that scene then picks: every layout holds the identical
+ *               floats.  NaN, Inf and negative texels included -- there is nothing here but the same multiplications and additions.
+ * The result is a pure function of the inputs: list order, list cuts, launch shape and stream do not change a bit.
+ *   out [K][Nt][3] dev: only listed texels are written.  texel_ids NULL => all Nt (n_ids ignored); a non-null list with n_ids == 0 is a no-op.
+ *   workspace: texir_irt_multi_workspace_bytes(n_ids, N, K) bytes of device scratch (12 bytes x K x parts per listed texel: callers cut long lists into
+ *   slices that are multiples of 64 texels -- scene.Scene.irt_multi does; 0 is returned for arguments the call refuses).
+ * Caller-owned buffers, the caller's stream, no allocation, no synchronisation, no atomics on results: the call records into a hipGraph, and a replay reads
+ * whatever tex holds then.  K outside 1..8 (reported before any null buffer), null tex, N < 1, a workspace that is too small and a scene without the
+ * 4-wide tree (TEXIR_BVH_WIDTH=2) are errors with a texir_last_error() text. */
+TEXIR_API int64_t texir_irt_multi_workspace_bytes(int64_t n_ids, int32_t N, int32_t K);
+TEXIR_API int texir_irt_multi(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const float* shift /*dev*/,
+                       const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode, const float* tex /*dev [Ht][Wt][K][3]*/,
+                       int32_t K, float* out /*dev [K][Nt][3]*/, void* workspace /*dev*/, int64_t workspace_bytes, void* stream);
+
 /* name of the kernel form ONE texir_irt_generate call over n_ids listed texels at N samples launches on this scene
  * ("irt_group_kernel<false, 4, 6>": 64 texels per wave; "irt_kernel<false, 4|2>": one texel per wave) -- the launcher's own
  * decision, so that bench.py's roofline names the kernel that really ran.  buf receives a NUL-terminated string. */

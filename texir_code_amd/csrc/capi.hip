@@ -468,6 +468,32 @@ int texir_irt_split(const texir_scene* s, const float* pos, const float* nrm, co
     return TEXIR_OK;
 }
 
+int64_t texir_irt_multi_workspace_bytes(int64_t n_ids, int32_t N, int32_t K)
+{
+    return (int64_t)irt_multi_workspace_bytes(n_ids, N, K);
+}
+
+int texir_irt_multi(const texir_scene* s, const float* pos, const float* nrm, const float* shift, const int32_t* texel_ids, int64_t n_ids, int64_t Nt,
+                    int32_t N, int32_t mode, const float* tex, int32_t K, float* out, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    // (K first: a caller that sized `tex` and `out` by a bad K may hold no buffer at all)
+    if (K < 1 || K > 8) return fail(TEXIR_ERR_INVALID, "texir_irt_multi: K must be in 1..8, got %d (call again for further textures: the results are independent)", K);
+    if (!tex) return fail(TEXIR_ERR_INVALID, "texir_irt_multi: tex is null");
+    if (!s || !pos || !nrm || !shift || !out) return fail(TEXIR_ERR_INVALID, "texir_irt_multi: null argument");
+    if (mode < 0 || mode > 1) return fail(TEXIR_ERR_INVALID, "texir_irt_multi: mode must be uniform(0) or cosine(1), got %d", mode);
+    if (N < 1 || Nt < 0 || n_ids < 0) return fail(TEXIR_ERR_INVALID, "texir_irt_multi: bad sizes N=%d Nt=%lld n_ids=%lld", N, (long long)Nt, (long long)n_ids);
+    if (Nt >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "texir_irt_multi: Nt too large");
+    if (!s->dev.nodes4) return fail(TEXIR_ERR_INVALID, "texir_irt_multi: the scene has no 4-wide tree (TEXIR_BVH_WIDTH=2 or the binary fallback): the pass has the 64-texel form only");
+    const int64_t n = texel_ids ? n_ids : Nt;
+    if (n == 0) return TEXIR_OK;
+    const int64_t need = (int64_t)irt_multi_workspace_bytes(n, N, K);
+    if (!workspace || workspace_bytes < need)
+        return fail(TEXIR_ERR_INVALID, "texir_irt_multi: the workspace holds %lld bytes, the call needs %lld (texir_irt_multi_workspace_bytes)",
+                    (long long)(workspace ? workspace_bytes : 0), (long long)need);
+    HIP_TRY(launch_irt_multi(dev_of(s, true), tex, pos, nrm, shift, texel_ids, n, Nt, N, mode, K, out, (float*)workspace, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 int texir_scene_reserve_scratch(texir_scene* s, int64_t n_ids, int32_t N)
 {
     if (!s || n_ids < 0 || N <= 0) return fail(TEXIR_ERR_INVALID, "texir_scene_reserve_scratch: bad argument");

@@ -86,6 +86,11 @@ size_t irt_split_workspace_bytes(int64_t n_ids, int N, int K);       // 0 for ar
 hipError_t launch_irt_split(const SceneDev& sc, const float* tex_row_major, const uint8_t* labels, const float* pos, const float* nrm, const float* shift,
                             const int32_t* ids /*nullable: all Nt*/, int64_t n_ids, int64_t Nt, int N, int mode, int K, int unit, float* out /*[K][Nt][3]*/,
                             float* partial /*>= irt_split_workspace_bytes()*/, hipStream_t st);
+// irtmulti.hip: the IrT estimator on K caller-owned textures in one traced pass (the same plan; needs the 4-wide tree)
+size_t irt_multi_workspace_bytes(int64_t n_ids, int N, int K);       // 0 for arguments the launch would refuse
+hipError_t launch_irt_multi(const SceneDev& sc, const float* tex /*dev [Ht][Wt][K][3]*/, const float* pos, const float* nrm, const float* shift,
+                            const int32_t* ids /*nullable: all Nt*/, int64_t n_ids, int64_t Nt, int N, int mode, int K, float* out /*[K][Nt][3]*/,
+                            float* partial /*>= irt_multi_workspace_bytes()*/, hipStream_t st);
 // irtlight.hip: direct irradiance factors of inserted area lights (quads, spheres) per listed texel, one closest-hit (any = true: any-hit, same bits) query per sample
 hipError_t launch_irt_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt,
                              const float* lights /*dev [K][16]*/, int K, int S, float t_max, float* F /*[K][Nt]*/, unsigned long long* stats /*nullable*/, hipStream_t st,

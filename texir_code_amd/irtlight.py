@@ -2,7 +2,12 @@
 
 Irradiance is linear in emitted radiance.  With F[k] the per-texel geometry-and-visibility factor of light k (traced once, Scene.irt_lights), the
 irradiance with the lights switched on at radiance colours[k] is E + sum_k colours[k] * F[k] -- what the "moving" half of the reference's relighting demo
-(tools/relighting_varying.py) leaves to an external renderer.  Direct light only."""
+(tools/relighting_varying.py) leaves to an external renderer.
+
+Bounce light.  Under light k texel y throws back the radiance albedo(y) / pi * colours[k] * F[k](y); its irradiance elsewhere is the IrT estimator on that
+radiance as the texture (Scene.irt_multi, K textures in one traced pass): bounce_textures / bounce / add_indirect, and add_view(G=...) for a view.
+Computed: the direct light of the new emitters and its bounces off the scene's DIFFUSE albedo.  Not computed: the shadow an emitter's own body casts on
+the captured light, and any specular bounce."""
 import json
 
 import numpy as np
@@ -102,10 +107,12 @@ def add(E, F, colours):
     return out
 
 
-def add_view(rgb, albedo, F, R, colours):
+def add_view(rgb, albedo, F, R, colours, G=None):
     """a view relit by inserted emitters: rgb + sum_k colours[k] * (albedo / pi * F[k] + R[k]).  rgb, albedo [...,3]; F [K,...] the lights' irradiance
     factors at the view's pixels (Scene.irt_lights), R [K,...] their specular response factors (Scene.spec_lights); colours [K] scalars or [K,3] -> [...,3].
-    numpy or torch; the terms are added in ascending k"""
+    G: the lights' bounce irradiance at the view's pixels (bounce), [K,...,3] per unit colour -- then colours[k] * (albedo / pi * G[k]) is added too, after
+    the direct terms -- or [...,3], already weighted and summed over the lights (add_indirect on zeros): albedo / pi * G is added.  With G=None the result
+    is what it was without the keyword, bit for bit.  numpy or torch; the terms are added in ascending k"""
     if len(colours) != F.shape[0] or tuple(R.shape) != tuple(F.shape):
         raise ValueError("%d colours, F %r, R %r: one colour per light and R shaped as F" % (len(colours), tuple(F.shape), tuple(R.shape)))
     if tuple(F.shape[1:]) != tuple(rgb.shape[:-1]) or rgb.shape[-1] != 3 or tuple(albedo.shape) != tuple(rgb.shape):
@@ -114,4 +121,96 @@ def add_view(rgb, albedo, F, R, colours):
     pi = _colour([PI32], rgb)                     # (an array, not a scalar: a torch division by a Python scalar multiplies by its reciprocal)
     for k in range(F.shape[0]):
         out = out + (albedo / pi * F[k][..., None] + R[k][..., None]) * _colour(colours[k], rgb)
+    if G is not None:
+        if tuple(G.shape) == tuple(rgb.shape):
+            out = out + albedo / pi * G
+        elif tuple(G.shape) == (F.shape[0],) + tuple(rgb.shape):
+            for k in range(F.shape[0]):
+                out = out + (albedo / pi * G[k]) * _colour(colours[k], rgb)
+        else:
+            raise ValueError("G %r must be [K,...,3] = %r or the summed [...,3]" % (tuple(G.shape), (F.shape[0],) + tuple(rgb.shape)))
     return out
+
+
+def add_indirect(E, G, colours):
+    """E + sum_k colours[k] * G[k]: E [...,3] an irradiance (add's result), G [K,...,3] the lights' bounce irradiance per unit colour (bounce), colours [K]
+    scalars or [K,3] -> [...,3].  numpy or torch; the terms are added in ascending k"""
+    if len(colours) != G.shape[0]:
+        raise ValueError("%d colours for %d lights" % (len(colours), G.shape[0]))
+    if tuple(G.shape[1:]) != tuple(E.shape) or E.shape[-1] != 3:
+        raise ValueError("E %r and G %r do not match ([...,3] and [K,...,3])" % (tuple(E.shape), tuple(G.shape)))
+    out = E
+    for k in range(G.shape[0]):
+        out = out + G[k] * _colour(colours[k], E)
+    return out
+
+
+def _resized(img, hw):
+    """[n,H,W,c] -> [n,Ht,Wt,c]: nothing when the size is hw already, else bilinear (align_corners=False), antialiased when an axis shrinks"""
+    import torch
+    H, W = int(img.shape[1]), int(img.shape[2])
+    if (H, W) == tuple(hw):
+        return img
+    x = torch.nn.functional.interpolate(img.permute(0, 3, 1, 2), size=tuple(hw), mode="bilinear", align_corners=False, antialias=hw[0] < H or hw[1] < W)
+    return x.permute(0, 2, 3, 1)
+
+
+def bounce_textures(albedo, F, tex_hw, src=None):
+    """the radiance the scene throws back under K lights of unit colour, as textures for Scene.irt_multi: albedo [Ha,Wa,3] and F [K,H,W] (irt_lights'
+    factors) or [K,H,W,3] (a bounce's irradiance), both in FILE orientation -> float32 [K,Ht,Wt,3] = (albedo / pi) * F[k] in the SCENE's orientation
+    (rows reversed, as models.py holds hdr_texture and labels), tex_hw = (Ht, Wt) the scene's texture size.  An image of another size is resized
+    first (bilinear, align_corners=False, antialiased when it shrinks); one of that size is used as it is, unrounded.  src: int [Ht,Wt], file
+    orientation, the nearest-covered-texel map texpost.pad_texture(cover, return_src=True) gives for the COVERAGE image (-1: no source): an uncovered
+    texel takes its source's radiance, so that bilinear footprints at chart edges do not darken; a covered texel keeps its own value, F = 0 (a shadow)
+    included.  src=None: nothing is filled.  numpy or torch in, torch out (on F's device)"""
+    import torch
+    Ht, Wt = int(tex_hw[0]), int(tex_hw[1])
+    F = torch.as_tensor(F)
+    dev = F.device
+    F = F.to(torch.float32)
+    albedo = torch.as_tensor(albedo).to(device=dev, dtype=torch.float32)
+    if albedo.ndim != 3 or albedo.shape[-1] != 3:
+        raise ValueError("albedo must be [Ha,Wa,3], got %r" % (tuple(albedo.shape),))
+    if F.ndim == 3:
+        F = F[..., None]
+    if F.ndim != 4 or F.shape[-1] not in (1, 3):
+        raise ValueError("F must be [K,H,W] or [K,H,W,3], got %r" % (tuple(F.shape),))
+    if Ht < 1 or Wt < 1:
+        raise ValueError("tex_hw must be positive, got %r" % (tuple(tex_hw),))
+    pi = torch.tensor([PI32], dtype=torch.float32, device=dev)            # (a tensor: see add_view)
+    rad = (_resized(albedo[None], (Ht, Wt))[0] / pi) * _resized(F, (Ht, Wt))
+    if src is not None:
+        s = torch.as_tensor(src).to(dev)
+        if tuple(s.shape) != (Ht, Wt):
+            raise ValueError("src must be [%d,%d] (the coverage map of the texture), got %r" % (Ht, Wt, tuple(s.shape)))
+        s = s.reshape(-1).long()
+        flat = rad.reshape(rad.shape[0], Ht * Wt, 3)
+        rad = torch.where((s >= 0)[None, :, None], flat[:, s.clamp(min=0)], flat).reshape(-1, Ht, Wt, 3)
+    return torch.flip(rad, dims=(1,)).contiguous()
+
+
+def bounce(scene, pos, nrm, shift, albedo, F, n_samples, bounces=1, texel_ids=None, hw=None, src=None):
+    """the bounce irradiance of K inserted lights of unit colour at the listed points: G [K,Nt,3] = sum over b = 1..bounces of G_b, added in ascending b,
+    G_1 = scene.irt_multi(bounce_textures(albedo, F)), G_b = scene.irt_multi(bounce_textures(albedo, G_{b-1})).  pos / nrm / shift [Nt,...] are the texel
+    list of an hw = (H, W) atlas in file orientation (default: F's own H, W), so that G_{b-1} is an image again; albedo, F, src: as bounce_textures takes
+    them.  Diffuse bounces of the NEW light only (see the module's docstring)"""
+    import torch
+    bounces = int(bounces)
+    if bounces < 1:
+        raise ValueError("bounces must be >= 1, got %d" % bounces)
+    F = torch.as_tensor(F)
+    if F.ndim not in (3, 4):
+        raise ValueError("F must be [K,H,W] or [K,H,W,3], got %r" % (tuple(F.shape),))
+    K = int(F.shape[0])
+    H, W = (int(v) for v in (hw if hw is not None else F.shape[1:3]))
+    Nt = int(pos.shape[0]) if pos.ndim == 2 else int(np.prod(pos.shape[:-1]))
+    if bounces > 1 and Nt != H * W:
+        raise ValueError("%d points are not the texels of a %d x %d atlas: a second bounce needs the whole atlas" % (Nt, H, W))
+    tex_hw = tuple(int(v) for v in scene.tex_shape[:2])
+    total, last = None, F
+    for b in range(1, bounces + 1):
+        last = scene.irt_multi(pos, nrm, shift, n_samples, bounce_textures(albedo, last, tex_hw, src), texel_ids=texel_ids)
+        total = last if total is None else total + last
+        if b < bounces:
+            last = last.reshape(K, H, W, 3)
+    return total

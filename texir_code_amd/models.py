@@ -74,6 +74,62 @@ def irt_light_query(value):
     return v
 
 
+def irt_light_bounce_settings(conf, lights, default_samples):
+    """the optional keys of the inserted emitters' bounce light (irtlight.bounce), read only when train.irt_lights names lights:
+      train.irt_light_bounces = 0 (default: no bounce files) | n >= 1 diffuse bounces of the new light;
+      train.irt_light_albedo = <albedo texture file in file orientation (.hdr or .png)> | <one float>: required with n >= 1 -- the stage runs before the
+                               material stage, so the albedo comes from an earlier run or is a constant;
+      train.irt_light_bounce_samples = samples per texel and bounce (default: the stage's own sample count).
+    -> (bounces, albedo, samples), albedo a float or a path; bad values raise ValueError"""
+    n = conf.get("train.irt_light_bounces", 0)
+    try:
+        if isinstance(n, bool) or int(n) != float(n) or int(n) < 0:
+            raise ValueError
+        n = int(n)
+    except (TypeError, ValueError):
+        raise ValueError("train.irt_light_bounces must be an integer >= 0, got %r" % (n,))
+    if n == 0 or str(lights).lower() == "none":
+        return 0, None, int(default_samples)
+    albedo = conf.get("train.irt_light_albedo", None)
+    if albedo is None or isinstance(albedo, bool) or str(albedo).strip() == "":
+        raise ValueError("train.irt_light_bounces = %d needs train.irt_light_albedo = <albedo texture file> | <one float>" % n)
+    try:
+        albedo = float(albedo)
+    except (TypeError, ValueError):
+        albedo = str(albedo)                      # a file name
+    if isinstance(albedo, float) and not (np.isfinite(albedo) and albedo >= 0.0):
+        raise ValueError("train.irt_light_albedo must be a finite number >= 0 or a file, got %r" % albedo)
+    s = conf.get("train.irt_light_bounce_samples", default_samples)
+    try:
+        if isinstance(s, bool) or int(s) != float(s) or int(s) < 1:
+            raise ValueError
+        s = int(s)
+    except (TypeError, ValueError):
+        raise ValueError("train.irt_light_bounce_samples must be an integer >= 1, got %r" % (s,))
+    return n, albedo, s
+
+
+def load_albedo_image(spec):
+    """train.irt_light_albedo -> float32 [Ha,Wa,3] in file orientation: one float (a 1 x 1 image: every resize of it is that constant), an .hdr, or a
+    .png (8 / 16 bit, scaled to 0..1)"""
+    if isinstance(spec, float):
+        return np.full((1, 1, 3), spec, np.float32)
+    if not os.path.exists(spec):
+        raise FileNotFoundError("train.irt_light_albedo = %s: no such file" % spec)
+    if spec.lower().endswith(".hdr"):
+        img = np.asarray(IO.read_hdr(spec), np.float32)
+    else:
+        raw = IO.read_png(spec)
+        img = raw.astype(np.float32) / np.float32(np.iinfo(raw.dtype).max)
+    if img.ndim == 2:
+        img = img[..., None]
+    if img.shape[-1] == 1:
+        img = np.repeat(img, 3, -1)
+    if img.ndim != 3 or img.shape[-1] < 3:
+        raise ValueError("train.irt_light_albedo = %s: expected an RGB image, got %r" % (spec, img.shape))
+    return np.ascontiguousarray(img[..., :3], np.float32)
+
+
 def seam_texels(index_texture):
     """texels the reference zeroes: `index_texture[:,:,0] + index_texture[:,:,1] + index_texture[:,:,2] == 0` evaluated in the image's own
     uint16 arithmetic (tracer_o3d_irt.py:137,176): a code triple whose sum wraps to 65536 counts as a seam there, and so it does here"""
@@ -157,6 +213,10 @@ class TracerO3d(nn.Module):
         # train.irt_light_query (optional key): closest (default) | any: the light pass's visibility as an occlusion query (Scene.irt_lights(query=...): same files)
         self.irt_light_query = irt_light_query(conf.get("train.irt_light_query", "closest"))
         self.ir_lights = None
+        # train.irt_light_bounces / irt_light_albedo / irt_light_bounce_samples (optional keys, irt_light_bounce_settings above): forward() also gathers the
+        # diffuse bounces of the inserted emitters' light (irtlight.bounce: Scene.irt_multi, all lights in one traced pass per bounce)
+        self.irt_light_bounces, self.irt_light_albedo, self.irt_light_bounce_samples = irt_light_bounce_settings(conf, self.irt_lights, int(self.sample_l[0]))
+        self.ir_lights_bounce = None
         # optional exact texel G-buffer written by the synthetic generator (bypasses the panorama gather)
         self.texel_gbuffer_path = _sibling(self.path_traced_mesh, "texel_gbuffer.npz")
 
@@ -287,6 +347,16 @@ class TracerO3d(nn.Module):
                 records, _ = irtlight.load(self.irt_lights)
                 self.ir_lights = self.scene.irt_lights(pos, nrm, shift, torch.from_numpy(records), self.irt_light_samples, texel_ids=ids,
                                                         query=self.irt_light_query).reshape(-1, H, W)
+            if self.irt_light_bounces >= 1:
+                with phases.phase("irt_light_bounce"):
+                    from . import texpost
+                    albedo = torch.from_numpy(load_albedo_image(self.irt_light_albedo)).to(self.device)
+                    # gutters take their nearest covered texel's radiance where the atlas and the radiance texture share a grid (irtlight.bounce_textures)
+                    src = None
+                    if (H, W) == tuple(self.scene.tex_shape[:2]):
+                        src = texpost.pad_texture((~seam).reshape(H, W, 1).to(torch.float32), return_src=True)[1]
+                    self.ir_lights_bounce = irtlight.bounce(self.scene, pos, nrm, shift, albedo, self.ir_lights, self.irt_light_bounce_samples,
+                                                            bounces=self.irt_light_bounces, texel_ids=ids, hw=(H, W), src=src).reshape(-1, H, W, 3)
         self.ir_texture = irr.reshape(H, W, 3)
         return self.ir_texture
 

@@ -227,6 +227,55 @@ class Scene:
                                          K, int(bool(unit)), _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()))
         return out
 
+    # -- several radiance textures in one traced pass (include/texir_hip.h texir_irt_multi) ----------------
+    def irt_multi(self, pos, nrm, shift, n_samples, textures, mode="uniform", texel_ids=None, out=None, max_workspace_bytes=4 << 30, interleaved=False):
+        """the IrT estimator on K caller-owned textures in one traced pass: textures [K,Ht,Wt,3] float32 in the orientation (and of the size) of the
+        scene's texture, K in 1..8 -> out [K, Nt, 3]; out[k] is bit for bit what irt_generate in its 64-texel form gives after set_texture(textures[k]).
+        The scene's own texture is neither read nor changed.  interleaved=True: textures is [Ht,Wt,K,3], the form the kernel reads, and a contiguous
+        float32 device tensor is used in place (a recorded graph replays with whatever it holds then); otherwise one permute().contiguous() makes that
+        copy.  Any point list: texels or a view's pixels.  The id list is walked in slices that are multiples of 64 texels so that the partial-sum
+        workspace stays under max_workspace_bytes; the cuts do not change a bit.  Only listed texels are written."""
+        pos = _dev_f32(pos, self.device).reshape(-1, 3)
+        nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
+        Nt = pos.shape[0]
+        shift = _dev_f32(shift, self.device).reshape(Nt, 2)
+        N = int(n_samples)
+        if not torch.is_tensor(textures):
+            textures = torch.from_numpy(np.ascontiguousarray(textures, dtype=np.float32))
+        Ht, Wt = (int(v) for v in self.tex_shape[:2])
+        want = (Ht, Wt, -1, 3) if interleaved else (-1, Ht, Wt, 3)
+        if textures.ndim != 4 or any(w >= 0 and int(s) != w for s, w in zip(textures.shape, want)):
+            raise ValueError("textures must be %s, got %r" % ("[%d,%d,K,3] (interleaved)" % (Ht, Wt) if interleaved else "[K,%d,%d,3]" % (Ht, Wt), tuple(textures.shape)))
+        K = int(textures.shape[2 if interleaved else 0])
+        tex = textures.to(device=self.device, dtype=torch.float32)
+        tex = tex.contiguous() if interleaved else tex.permute(1, 2, 0, 3).contiguous()
+        if out is None:
+            out = torch.zeros((K, Nt, 3), device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (K, Nt, 3) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 [%d,%d,3]" % (K, Nt))
+        ids = None
+        n = Nt
+        if texel_ids is not None:
+            ids = texel_ids.to(device=self.device, dtype=torch.int32).contiguous()
+            n = ids.numel()
+        if n == 0:
+            return out
+        L = _lib.lib()
+        per_texel = int(L.texir_irt_multi_workspace_bytes(1, N, K))       # (0 for arguments the library refuses: the call below then reports them)
+        step = n
+        if per_texel > 0 and per_texel * n > int(max_workspace_bytes):
+            step = max(64, int(max_workspace_bytes) // per_texel // 64 * 64)
+            if ids is None:
+                ids = torch.arange(Nt, device=self.device, dtype=torch.int32)
+        ws_bytes = max(per_texel * step, 16)
+        ws = torch.empty(ws_bytes, device=self.device, dtype=torch.uint8)
+        for first in range(0, n, step):
+            cnt = min(step, n - first)
+            part = None if ids is None else ids[first:first + cnt]
+            _lib.check(L.texir_irt_multi(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(part), cnt, Nt, N, MODES[mode], _lib.ptr(tex) if K else None,
+                                         K, _lib.ptr(out) if K else None, _lib.ptr(ws), ws_bytes, _lib.stream_ptr()))
+        return out
+
     # -- inserted emitters (include/texir_hip.h texir_irt_lights) ------------------------------------------
     def irt_lights(self, pos, nrm, shift, lights, n_samples, texel_ids=None, t_max=0.999, out=None, stats=False, query="closest"):
         """direct irradiance factors of inserted area lights: lights [K,16] float32 records (irtlight.pack; a device tensor is used in place, so a

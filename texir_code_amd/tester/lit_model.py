@@ -2,15 +2,24 @@
 
     test.lights = none | <json of inserted emitters, the file form of train.irt_lights (irtlight.load)>
     test.light_samples = 64
+    test.light_bounces = 0            diffuse bounces of the new light (irtlight.bounce), gathered once at construction on the irradiance texture's grid
+    test.light_bounce_samples = 256   samples per texel and bounce
 
 With lights, render() adds their diffuse and specular response to every rendered view, sum_k colour_k (albedo / pi F[k] + R[k]) (Scene.irt_lights,
 Scene.spec_lights, irtlight.add_view), at test.light_samples samples per pixel, light and technique, with the pixels' own specular shift and the model's
-floor of denominators.  With the default `none` the class IS its base: every file Editing, View, Relighting and Error write is unchanged byte for byte.
+floor of denominators.  With test.light_bounces >= 1 the model also builds, once, a texel G-buffer of irt.hdr's size, the lights' factors F per texel, and
+G = irtlight.bounce(...) with the albedo texture as the diffuse albedo; it keeps sum_k colour_k G[k] as a texture in file orientation, forward() fetches
+it with the very call that fetches the irradiance texture, and render() adds albedo / pi times that.  The texel shifts come from a private generator with a
+fixed seed: the CPU generator's stream stays what it is.  Not computed: the shadow an emitter's body casts on the captured light, a specular bounce.
+With the default `none` the class IS its base: every file Editing, View, Relighting and Error write is unchanged byte for byte.
 This is the class the plugin registry hands the tester runners for models.test_nvdiffrast.MaterialModel."""
 import torch
 
-from .. import irtlight
+from .. import gbuffer as GB, irtlight, texpost
+from ..texture import texture as tex_fetch
 from . import test_model as TM
+
+BOUNCE_SEED = 20241                       # the private generator of the texel shifts
 
 
 def load_test_lights(spec, device):
@@ -21,11 +30,60 @@ def load_test_lights(spec, device):
     return torch.from_numpy(records).to(device), torch.from_numpy(colours).to(device)
 
 
+def light_bounce_settings(conf):
+    """test.light_bounces (0) and test.light_bounce_samples (256) -> (bounces >= 0, samples >= 1); bad values raise ValueError"""
+    out = []
+    for key, default, least in (("test.light_bounces", 0, 0), ("test.light_bounce_samples", 256, 1)):
+        v = conf.get(key, default)
+        try:
+            if isinstance(v, bool) or int(v) != float(v) or int(v) < least:
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError("%s must be an integer >= %d, got %r" % (key, least, v))
+        out.append(int(v))
+    return tuple(out)
+
+
 class MaterialModel(TM.MaterialModel):
     def __init__(self, conf, *args, **kwargs):
         super().__init__(conf, *args, **kwargs)
         self.test_lights = load_test_lights(str(conf.get("test.lights", "none")), self.device)
         self.light_samples = int(conf.get("test.light_samples", 64))
+        self.light_bounces, self.light_bounce_samples = light_bounce_settings(conf)
+        self.bounce_tex = None
+        if self.test_lights is not None and self.light_bounces >= 1:
+            self.build_bounce_texture()
+
+    def build_bounce_texture(self):
+        """sum_k colour_k G[k] on the irradiance texture's grid, file orientation -> self.bounce_tex [H,W,3] (device)"""
+        records, colours = self.test_lights
+        H, W = int(self.irrt.shape[0]), int(self.irrt.shape[1])
+        pos, nrm, prim, _ = GB.raster_texel_gbuffer(self.scene, H, W, normal="geometric", offset=1e-2, want_ids=True)
+        covered = (prim >= 0).reshape(-1)
+        ids = torch.nonzero(covered)[:, 0].to(torch.int32)
+        gen = torch.Generator().manual_seed(BOUNCE_SEED)
+        shift = torch.rand(H * W, 2, generator=gen).to(self.device)
+        pos, nrm = pos.reshape(-1, 3).contiguous(), nrm.reshape(-1, 3).contiguous()
+        F = self.scene.irt_lights(pos, nrm, shift, records, int(self.light_samples), texel_ids=ids).reshape(-1, H, W)
+        src = None
+        if (H, W) == tuple(self.scene.tex_shape[:2]):
+            src = texpost.pad_texture(covered.reshape(H, W, 1).to(torch.float32), return_src=True)[1]
+        albedo = self.materials_a.detach().to(self.device)                  # file orientation, as irt.hdr: forward() fetches both with one uv
+        G = irtlight.bounce(self.scene, pos, nrm, shift, albedo, F, int(self.light_bounce_samples), bounces=int(self.light_bounces), texel_ids=ids,
+                            hw=(H, W), src=src).reshape(-1, H, W, 3)
+        self.bounce_tex = irtlight.add_indirect(torch.zeros((H, W, 3), device=self.device), G, colours).contiguous()
+        return self.bounce_tex
+
+    def forward(self, mvp, id, cam_position, *args, **kwargs):
+        tex = getattr(self, "bounce_tex", None)
+        if tex is None:
+            return super().forward(mvp, id, cam_position, *args, **kwargs)
+        gb = self._gbuffer(mvp, id)                                          # (cached: the base's own call below gets the same G-buffer)
+        self._bounce_irr = tex_fetch(tex, gb["uv"], gb["uv_da"], "linear-mipmap-linear", self.max_mip_level)
+        try:
+            return super().forward(mvp, id, cam_position, *args, **kwargs)
+        finally:
+            self._bounce_irr = None
 
     def render(self, normal, albedo, roughness, points, cam_position, irr):
         lights = getattr(self, "test_lights", None)
@@ -46,5 +104,6 @@ class MaterialModel(TM.MaterialModel):
         pts, nrm, alb = points.reshape(P, 3), normal.reshape(P, 3), albedo.reshape(P, 3)
         F = self.scene.irt_lights(pts, nrm, shift_s, records, n_l)
         R = self.scene.spec_lights(pts, nrm, roughness.reshape(P), shift_s, cam_position, records, n_l, clamp_eps=TM.TINY_NUMBER)
-        res["rgb"] = irtlight.add_view(res["rgb"].reshape(P, 3), alb, F, R, colours).reshape(shape + (3,))
+        G = getattr(self, "_bounce_irr", None)
+        res["rgb"] = irtlight.add_view(res["rgb"].reshape(P, 3), alb, F, R, colours, G=None if G is None else G.reshape(P, 3)).reshape(shape + (3,))
         return res

@@ -47,11 +47,12 @@ From the files an IrT stage with train.irt_split wrote into <dir> (0_irr_texture
 class off).  --replace: class k's texels become ONE colour instead, colour * 0_irr_texture_unit<k>.hdr (train.irt_split_unit; the reference's "lamp texels
 become one colour", models/test_nvdiffrast.py:109-110).  Irradiance is linear in the radiance texture: nothing is traced.  Existing files are not overwritten.
 
-    python -m texir_code_amd.tools light-irt <dir> --light k --colour r,g,b [--light j --colour r,g,b ...] [--base <file>]
+    python -m texir_code_amd.tools light-irt <dir> --light k --colour r,g,b [--light j --colour r,g,b ...] [--base <file>] [--bounce]
 
 From the files an IrT stage with train.irt_lights wrote into <dir> (0_irr_texture_light<k>.hdr, the irradiance under inserted emitter k at unit radiance):
-0_irr_texture_lit.hdr = base + sum colour_k * 0_irr_texture_light<k>.hdr -- the listed emitters switched on at those radiances (direct light only).  The
-base is <dir>/0_irr_texture.hdr, or --base <file>, e.g. a 0_irr_texture_relit.hdr from relight-irt.  Irradiance is linear in emitted radiance: nothing is
+0_irr_texture_lit.hdr = base + sum colour_k * 0_irr_texture_light<k>.hdr -- the listed emitters switched on at those radiances.  Direct light only,
+unless --bounce: then colour_k * 0_irr_texture_light<k>_bounce.hdr (train.irt_light_bounces: the new light's diffuse bounces) is added for every named
+light as well.  The base is <dir>/0_irr_texture.hdr, or --base <file>, e.g. a 0_irr_texture_relit.hdr from relight-irt.  Irradiance is linear in emitted radiance: nothing is
 traced.  Existing files are not overwritten.
 """
 import sys
@@ -199,8 +200,9 @@ def relight_irt(directory, k, colour, replace=False):
     return dst
 
 
-def light_irt(directory, lights, base=None):
-    """lights: [(k, (r, g, b)), ...] -> the path written.  FileExistsError / FileNotFoundError / ValueError name what is wrong"""
+def light_irt(directory, lights, base=None, bounce=False):
+    """lights: [(k, (r, g, b)), ...]; bounce: also the lights' bounce files -> the path written.  FileExistsError / FileNotFoundError / ValueError name
+    what is wrong"""
     import os
     from . import irtlight
     dst = os.path.join(directory, "0_irr_texture_lit.hdr")
@@ -222,13 +224,24 @@ def light_irt(directory, lights, base=None):
             raise ValueError("%s is %r, the base %s is %r" % (f, img.shape, base, E.shape))
         F.append(img[..., 0])
     out = irtlight.add(E, np.stack(F), [c for _, c in lights])
+    if bounce:
+        G = []
+        for k, _ in lights:
+            f = os.path.join(directory, "0_irr_texture_light%d_bounce.hdr" % k)
+            if not os.path.exists(f):
+                raise FileNotFoundError("--bounce needs %s: run the IrT stage with train.irt_light_bounces >= 1 (and train.irt_light_albedo)" % f)
+            img = np.asarray(IO.read_hdr(f), np.float32)
+            if img.shape != E.shape:
+                raise ValueError("%s is %r, the base %s is %r" % (f, img.shape, base, E.shape))
+            G.append(img)
+        out = irtlight.add_indirect(out, np.stack(G), [c for _, c in lights])
     IO.write_hdr(dst, np.ascontiguousarray(out, np.float32))
     return dst
 
 
 def main(argv):
     if len(argv) >= 2 and argv[0] == "light-irt":
-        rest, lights, base, bad = [], [], None, False
+        rest, lights, base, bad, bounce = [], [], None, False, False
         it = iter(argv[1:])
         for a in it:
             key, eq, val = a.partition("=")
@@ -248,15 +261,17 @@ def main(argv):
                         base = val
                 except (TypeError, ValueError, AttributeError):
                     bad = True
+            elif a == "--bounce":
+                bounce = True
             elif a.startswith("--"):
                 bad = True
             else:
                 rest.append(a)
         if bad or len(rest) != 1 or not lights or any(c is None for _, c in lights):
-            print("light-irt needs <dir> --light k --colour r,g,b [--light k --colour r,g,b ...] [--base <file>]")
+            print("light-irt needs <dir> --light k --colour r,g,b [--light k --colour r,g,b ...] [--base <file>] [--bounce]")
             return 2
         try:
-            dst = light_irt(rest[0], [(k, c) for k, c in lights], base)
+            dst = light_irt(rest[0], [(k, c) for k, c in lights], base, bounce)
         except (FileExistsError, FileNotFoundError) as e:
             print(e)
             return 1

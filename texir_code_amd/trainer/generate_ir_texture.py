@@ -95,6 +95,12 @@ class IrrTextureRunner:
                 with phases.phase("write_hdr", sync=False):
                     for k in range(lights.shape[0]):
                         IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_light%d.hdr" % k), lights[k][..., None].expand(-1, -1, 3).contiguous().cpu().numpy())
+            # train.irt_light_bounces (models.TracerO3d): the diffuse bounces of every inserted emitter's light at unit radiance, beside its direct file
+            bounce = getattr(self.model, "ir_lights_bounce", None)
+            if bounce is not None:
+                with phases.phase("write_hdr", sync=False):
+                    for k in range(bounce.shape[0]):
+                        IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_light%d_bounce.hdr" % k), bounce[k].contiguous().cpu().numpy())
         return irr_texture
 
     def _write_irt(self, irr_texture, path):
