@@ -225,6 +225,78 @@ TEXIR_API int texir_irt_multi(const texir_scene* scene, const float* pos /*dev*/
                        const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode, const float* tex /*dev [Ht][Wt][K][3]*/,
                        int32_t K, float* out /*dev [K][Nt][3]*/, void* workspace /*dev*/, int64_t workspace_bytes, void* stream);
 
+/* ---- the shadow an inserted emitter's BODY casts on the captured light, per texel (csrc/irtshadow.hip).  texir_irt_lights, texir_spec_lights and
+ * texir_irt_multi build the response to a NEW lamp; each of them only ever adds light.  This call gives the one term of a relit room with the other sign:
+ * the part of a texel's captured irradiance that arrived along rays the lamp's body now intercepts.
+ *
+ * THE RULE.  Inputs: everything texir_irt_generate takes; bodies: K in 0..8 records of 16 float32 in DEVICE memory, the layout and the validity rule of
+ * texir_irt_lights (a replayed graph sees moved bodies, so the host never validates a record); sets: M in 1..8 uint32 bit masks over the bodies in DEVICE
+ * memory -- bit k = body k; {k} is the shadow of lamp k alone, all bits the shadow of all of them together; bits at or above K are ignored; a zero mask
+ * yields zeros.
+ *   SAMPLES AND RAYS  directions d, ndl = n.l from the RAW normal, the ray (org = x = pos, dir = d), the acceptance test (slot >= 0 && t > 1e-4) and the
+ *               closest hit t_s are exactly those of irt_group_kernel<false, 4, 6>, texir_irt_generate's 64-texel form: one texel per lane, one sample
+ *               per pass.  L_i is the radiance the hit shader reads from the scene's OWN texture, in whatever layout it holds it.
+ *   BODIES      per sample, body k MEETS the ray at t_b (in units of |d|, as t_s is) under the rule below; B = the mask of bodies that meet it with
+ *               t_b < t_s.  A ray that meets no body is not traced (its sample adds nothing whatever it hits); nothing is skipped on ndl.
+ *   RESULT      lost[m] = (2 pi / N) sum_i L_i ndl_i [sample i has an accepted hit AND (sets[m] & B_i) != 0].  A set is evaluated from the per-ray mask:
+ *               the shadows of overlapping bodies are a union, not a sum.  The relit irradiance is max(E - lost[m], 0) + sum_k colour_k (F[k] + G[k])
+ *               (texir_code_amd/irtlight.py add).
+ *   REDUCTION   the 64-texel plan of texir_irt_multi under the same switches (TEXIR_IRT_MIN_PART_CELLS, TEXIR_IRT_LOG2PARTS): acc_m += L ndl per lane
+ *               over the passes of a part, in irt_group_kernel's pass order; partial[part][m][i][3]; the parts are added in part order;
+ *               out[m][t][c] = ((a * 2) * pi) / N.
+ *   CONSEQUENCE for a texel and a set under which EVERY sample with an accepted hit is blocked, lost[m] is, bit for bit, what texir_irt_generate in its
+ *               64-texel form (TEXIR_IRT_TEXELS_PER_WAVE=64, or any list of >= 32 768 texels) writes: the same additions in the same order.  For a set no
+ *               sample's ray meets, lost[m] is exactly +0.  The result is a pure function of the inputs: list order, duplicates, list cuts, launch
+ *               shape, stream and graph replay change no bit.
+ *
+ * BODY INTERSECTION RULE, as a FLOAT32 OPERATION SEQUENCE (each operation separately rounded, no contraction; sqrt and / correctly rounded).
+ *   record      valid as texir_irt_lights has it (kind 0.0f or 1.0f, finite words, a x b != 0 and finite, r > 0 and (fourpi32 r) r finite); a quad also needs
+ *               mm (below) finite and > 0.  Any other record never blocks.
+ *   QUAD, two-sided as an occluder (per record):
+ *               m_x = a_y b_z - a_z b_y,  m_y = a_z b_x - a_x b_z,  m_z = a_x b_y - a_y b_x;   mm = (m_x m_x + m_y m_y) + m_z m_z
+ *               ua = (b x m) / mm,  vb = (m x a) / mm,  each cross-product component p q - r s as for m, each quotient on its own (the reciprocal basis of
+ *               csrc/speclight.hip: h = u a + v b  ->  u = h.ua, v = h.vb)
+ *         (per sample):
+ *               den = (m_x d_x + m_y d_y) + m_z d_z;   q_i = o_i - x_i;   num = (m_x q_x + m_y q_y) + m_z q_z;   t = num / den
+ *               h_i = t * d_i - q_i;   u = (h_x ua_x + h_y ua_y) + h_z ua_z;   v = (h_x vb_x + h_y vb_y) + h_z vb_z
+ *               it MEETS the ray iff den != 0, t is finite, t > 0, 0 <= u <= 1 and 0 <= v <= 1;   t_b = t      (either side: the sign of den is not asked)
+ *   SPHERE, a solid ball:
+ *               rr = r * r (per record);   oc_i = c_i - x_i;   b = (oc_x d_x + oc_y d_y) + oc_z d_z;   dd = (d_x d_x + d_y d_y) + d_z d_z
+ *               cc = ((oc_x oc_x + oc_y oc_y) + oc_z oc_z) - rr;   disc = b * b - dd * cc;   s = b + sqrt(disc);   far = s / dd
+ *               it MEETS the ray iff disc >= 0 and far > 0 (the far root);   t_b = 0 when cc <= 0 (the texel is inside the ball), else t_b = cc / s, the near
+ *               root in its cancellation-free form
+ *   BLOCKED     t_b < t_s, both float32.
+ * ROUNDING BOUND (first order, u = 2^-24; x and the record are exact float32 values, d_i carries e_i per component; the tests multiply every bound by their
+ * factor K).  What depends on x and the record alone -- m, mm, ua, vb, q, num of a quad; rr, oc, cc of a sphere -- uses IEEE products, sums and quotients of
+ * exact float32 values only: a restatement on any IEEE machine gives the same bits, and the bounds below start from them as exact float32 values (as the
+ * bounds of texir_irt_lights start from s0 and s1).  This is what keeps the near root cc / s sharp where b - sqrt(disc) would cancel.
+ *     quad:    |dden| <= 3 u sum_i |m_i d_i| + sum_i |m_i| e_i;   |dt| <= |t| |dden| / |den| + u |t|;   the test t > 0 is decided unless |t| <= |dt|, and
+ *              den != 0 unless |den| <= |dden|
+ *              |dh_i| <= |d_i| |dt| + |t| e_i + u (|t d_i| + |h_i|)
+ *              |du| <= 3 u sum_i |h_i ua_i| + sum_i |ua_i| |dh_i|,  v alike;   a cut of u or v at 0 or 1 is decided unless within |du|, |dv|
+ *     sphere:  |db| <= 3 u sum_i |oc_i d_i| + sum_i |oc_i| e_i;   |ddd| <= 3 u dd + 2 sum_i |d_i| e_i
+ *              |ddisc| <= 2 |b| |db| + u b b + |cc| |ddd| + u |dd cc| + u |disc|;   the test disc >= 0 is decided unless |disc| <= |ddisc|
+ *              |dsq| <= min(|ddisc| / (2 sqrt(max(disc - |ddisc|, 0))), sqrt(|ddisc|)) + u sqrt(disc);   |ds| <= |db| + |dsq| + u |s|
+ *              far > 0 has the sign of s (dd > 0): decided unless |s| <= |ds|;   |dt_b| <= |t_b| |ds| / |s| + u |t_b|;   the cut cc <= 0 is exact
+ *     BLOCKED is decided unless |t_b - t_s| <= |dt_b| + bound(t_s), bound(t_s) the closest hit's own.
+ *
+ *   out [M][Nt][3] dev: only listed texels are written, zeros included (K = 0: zeros).  texel_ids NULL => all Nt (n_ids ignored); a non-null list with
+ *   n_ids == 0 is a no-op.
+ *   stats dev u64[2], nullable: += samples whose ray meets a body (the rays traced), and the blocked ones among them (an accepted hit behind a body, of
+ *   any set or none); one atomic add per wave and counter.
+ *   workspace: texir_irt_shadow_workspace_bytes(n_ids, N, M) bytes of device scratch (12 bytes x M x parts per listed texel: callers cut long lists into
+ *   slices that are multiples of 64 texels -- scene.Scene.irt_shadow does; 0 is returned for arguments the call refuses).
+ * Caller-owned buffers, the caller's stream, no allocation, no synchronisation, no atomics on results: the call records into a hipGraph, and a replay reads
+ * whatever bodies and sets hold then.  K outside 0..8 or M outside 1..8 (reported before any null buffer), a null buffer, N < 1, a workspace that is too
+ * small and a scene without the 4-wide tree (TEXIR_BVH_WIDTH=2) are errors with a texir_last_error() text.
+ * Not computed here: bodies shadowing each other's direct light F[j] or the bounce G, the body's shadow in the specular term of captured light, the body
+ * drawn in a view, triangle-mesh occluders. */
+TEXIR_API int64_t texir_irt_shadow_workspace_bytes(int64_t n_ids, int32_t N, int32_t M);
+TEXIR_API int texir_irt_shadow(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const float* shift /*dev*/,
+                       const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode, const float* bodies /*dev [K][16]*/,
+                       int32_t K /*0..8*/, const uint32_t* sets /*dev [M]*/, int32_t M /*1..8*/, float* out /*dev [M][Nt][3]*/,
+                       uint64_t* stats /*dev [2], nullable*/, void* workspace /*dev*/, int64_t workspace_bytes, void* stream);
+
 /* name of the kernel form ONE texir_irt_generate call over n_ids listed texels at N samples launches on this scene
  * ("irt_group_kernel<false, 4, 6>": 64 texels per wave; "irt_kernel<false, 4|2>": one texel per wave) -- the launcher's own
  * decision, so that bench.py's roofline names the kernel that really ran.  buf receives a NUL-terminated string. */

@@ -51,6 +51,8 @@ def signatures():
         "texir_irt_split": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, i32, vp, vp, i64, vp],
         "texir_irt_multi_workspace_bytes": (i64, [i64, i32, i32]),
         "texir_irt_multi": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, vp, vp, i64, vp],
+        "texir_irt_shadow_workspace_bytes": (i64, [i64, i32, i32]),
+        "texir_irt_shadow": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, vp, i32, vp, vp, vp, i64, vp],
         "texir_irt_kernel_name": [vp, i64, i32, text, i32],
         "texir_spec_forward": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp],
         "texir_spec_forward_train": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp, vp],

@@ -494,6 +494,36 @@ int texir_irt_multi(const texir_scene* s, const float* pos, const float* nrm, co
     return TEXIR_OK;
 }
 
+int64_t texir_irt_shadow_workspace_bytes(int64_t n_ids, int32_t N, int32_t M)
+{
+    return (int64_t)irt_shadow_workspace_bytes(n_ids, N, M);
+}
+
+int texir_irt_shadow(const texir_scene* s, const float* pos, const float* nrm, const float* shift, const int32_t* texel_ids, int64_t n_ids, int64_t Nt,
+                     int32_t N, int32_t mode, const float* bodies, int32_t K, const uint32_t* sets, int32_t M, float* out, uint64_t* stats, void* workspace,
+                     int64_t workspace_bytes, void* stream)
+{
+    // (K and M first: a caller that sized `bodies`, `sets` and `out` by a bad count may hold no buffer at all)
+    if (K < 0 || K > 8) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: K must be in 0..8, got %d (call again for further bodies and take the union of the sets on the caller's side)", K);
+    if (M < 1 || M > 8) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: M must be in 1..8, got %d (call again for further sets: the results are independent)", M);
+    if (K > 0 && !bodies) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: bodies is null");
+    if (!sets) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: sets is null");
+    if (!s || !pos || !nrm || !shift || !out) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: null argument");
+    if (mode < 0 || mode > 1) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: mode must be uniform(0) or cosine(1), got %d", mode);
+    if (N < 1 || Nt < 0 || n_ids < 0) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: bad sizes N=%d Nt=%lld n_ids=%lld", N, (long long)Nt, (long long)n_ids);
+    if (Nt >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: Nt too large");
+    const int64_t n = texel_ids ? n_ids : Nt;
+    if (n == 0) return TEXIR_OK;
+    const int64_t need = (int64_t)irt_shadow_workspace_bytes(n, N, M);
+    if (!workspace || workspace_bytes < need)
+        return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: the workspace holds %lld bytes, the call needs %lld (texir_irt_shadow_workspace_bytes)",
+                    (long long)(workspace ? workspace_bytes : 0), (long long)need);
+    if (!s->dev.nodes4) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: the scene has no 4-wide tree (TEXIR_BVH_WIDTH=2 or the binary fallback): the pass has the 64-texel form only");
+    HIP_TRY(launch_irt_shadow(dev_of(s, true), pos, nrm, shift, texel_ids, n, Nt, N, mode, bodies, K, sets, M, out, (unsigned long long*)stats, (float*)workspace,
+                              (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 int texir_scene_reserve_scratch(texir_scene* s, int64_t n_ids, int32_t N)
 {
     if (!s || n_ids < 0 || N <= 0) return fail(TEXIR_ERR_INVALID, "texir_scene_reserve_scratch: bad argument");

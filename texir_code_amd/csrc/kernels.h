@@ -91,6 +91,11 @@ size_t irt_multi_workspace_bytes(int64_t n_ids, int N, int K);       // 0 for ar
 hipError_t launch_irt_multi(const SceneDev& sc, const float* tex /*dev [Ht][Wt][K][3]*/, const float* pos, const float* nrm, const float* shift,
                             const int32_t* ids /*nullable: all Nt*/, int64_t n_ids, int64_t Nt, int N, int mode, int K, float* out /*[K][Nt][3]*/,
                             float* partial /*>= irt_multi_workspace_bytes()*/, hipStream_t st);
+// irtshadow.hip: what the bodies of inserted emitters (the records of launch_irt_lights) take from the captured light, per set of bodies (the same plan; 4-wide tree)
+size_t irt_shadow_workspace_bytes(int64_t n_ids, int N, int M);      // 0 for arguments the launch would refuse
+hipError_t launch_irt_shadow(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n_ids, int64_t Nt,
+                             int N, int mode, const float* bodies /*dev [K][16]*/, int K, const uint32_t* sets /*dev [M]*/, int M, float* out /*[M][Nt][3]*/,
+                             unsigned long long* stats /*nullable*/, float* partial /*>= irt_shadow_workspace_bytes()*/, hipStream_t st);
 // irtlight.hip: direct irradiance factors of inserted area lights (quads, spheres) per listed texel, one closest-hit (any = true: any-hit, same bits) query per sample
 hipError_t launch_irt_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt,
                              const float* lights /*dev [K][16]*/, int K, int S, float t_max, float* F /*[K][Nt]*/, unsigned long long* stats /*nullable*/, hipStream_t st,

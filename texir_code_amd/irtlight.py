@@ -6,8 +6,12 @@ irradiance with the lights switched on at radiance colours[k] is E + sum_k colou
 
 Bounce light.  Under light k texel y throws back the radiance albedo(y) / pi * colours[k] * F[k](y); its irradiance elsewhere is the IrT estimator on that
 radiance as the texture (Scene.irt_multi, K textures in one traced pass): bounce_textures / bounce / add_indirect, and add_view(G=...) for a view.
-Computed: the direct light of the new emitters and its bounces off the scene's DIFFUSE albedo.  Not computed: the shadow an emitter's own body casts on
-the captured light, and any specular bounce."""
+
+The body's shadow.  A lamp is a body too: Scene.irt_shadow gives, per set of bodies, the part `lost` of the captured irradiance E that arrived along rays
+a body of the set now intercepts; add(E, F, colours, lost=) and add_view(..., lost=) take it away, floored at zero, before the new light is added.
+Computed: the direct light of the new emitters, its bounces off the scene's DIFFUSE albedo, and the shadow the emitters' bodies cast on the captured
+DIFFUSE light.  Not computed: bodies shadowing each other's direct light or the bounce, the bodies' shadow in the specular term of captured light, the
+body drawn in a view, and any specular bounce."""
 import json
 
 import numpy as np
@@ -94,31 +98,52 @@ def _colour(c, like):
     return torch.as_tensor(c, dtype=like.dtype, device=like.device).reshape(-1)
 
 
-def add(E, F, colours):
+def _floor0(x):
+    if isinstance(x, np.ndarray):
+        return np.maximum(x, x.dtype.type(0))
+    return x.clamp(min=0)
+
+
+def add(E, F, colours, lost=None):
     """E + sum_k colours[k] * F[k][..., None]: E [...,3] the irradiance without the lights, F [K,...] their factors, colours [K] scalars or [K,3] emitted
-    radiances -> [...,3].  numpy or torch; the terms are added in ascending k"""
+    radiances -> [...,3].  lost [...,3]: what the lights' bodies take from E (Scene.irt_shadow, the set of the lights switched in) -- the sum then starts
+    from max(E - lost, 0); lost=None: the bits it returned without the keyword.  numpy or torch; the terms are added in ascending k"""
     if len(colours) != F.shape[0]:
         raise ValueError("%d colours for %d lights" % (len(colours), F.shape[0]))
     if tuple(F.shape[1:]) != tuple(E.shape[:-1]) or E.shape[-1] != 3:
         raise ValueError("E %r and F %r do not match ([...,3] and [K,...])" % (tuple(E.shape), tuple(F.shape)))
     out = E
+    if lost is not None:
+        if tuple(lost.shape) != tuple(E.shape):
+            raise ValueError("lost %r must be shaped as E %r" % (tuple(lost.shape), tuple(E.shape)))
+        out = _floor0(E - lost)
     for k in range(F.shape[0]):
         out = out + F[k][..., None] * _colour(colours[k], E)
     return out
 
 
-def add_view(rgb, albedo, F, R, colours, G=None):
+def add_view(rgb, albedo, F, R, colours, G=None, lost=None, irr=None):
     """a view relit by inserted emitters: rgb + sum_k colours[k] * (albedo / pi * F[k] + R[k]).  rgb, albedo [...,3]; F [K,...] the lights' irradiance
     factors at the view's pixels (Scene.irt_lights), R [K,...] their specular response factors (Scene.spec_lights); colours [K] scalars or [K,3] -> [...,3].
     G: the lights' bounce irradiance at the view's pixels (bounce), [K,...,3] per unit colour -- then colours[k] * (albedo / pi * G[k]) is added too, after
     the direct terms -- or [...,3], already weighted and summed over the lights (add_indirect on zeros): albedo / pi * G is added.  With G=None the result
-    is what it was without the keyword, bit for bit.  numpy or torch; the terms are added in ascending k"""
+    is what it was without the keyword, bit for bit.  lost [...,3]: what the lights' bodies take from the captured irradiance at the view's pixels
+    (Scene.irt_shadow), with irr [...,3] the captured irradiance rgb's diffuse term albedo / pi * irr was made of: the diffuse term becomes
+    albedo / pi * max(irr - lost, 0), i.e. albedo / pi * (irr - max(irr - lost, 0)) is taken from rgb before anything is added.  Without irr the
+    floor acts on the whole pixel: max(rgb - albedo / pi * lost, 0).  lost=None: the bits of the call without the keyword.  numpy or torch; the terms are added in ascending k"""
     if len(colours) != F.shape[0] or tuple(R.shape) != tuple(F.shape):
         raise ValueError("%d colours, F %r, R %r: one colour per light and R shaped as F" % (len(colours), tuple(F.shape), tuple(R.shape)))
     if tuple(F.shape[1:]) != tuple(rgb.shape[:-1]) or rgb.shape[-1] != 3 or tuple(albedo.shape) != tuple(rgb.shape):
         raise ValueError("rgb %r, albedo %r and F %r do not match ([...,3], [...,3] and [K,...])" % (tuple(rgb.shape), tuple(albedo.shape), tuple(F.shape)))
     out = rgb
     pi = _colour([PI32], rgb)                     # (an array, not a scalar: a torch division by a Python scalar multiplies by its reciprocal)
+    if lost is not None:
+        if tuple(lost.shape) != tuple(rgb.shape) or (irr is not None and tuple(irr.shape) != tuple(rgb.shape)):
+            raise ValueError("lost (and irr) must be shaped as rgb %r" % (tuple(rgb.shape),))
+        if irr is None:
+            out = _floor0(rgb - albedo / pi * lost)
+        else:
+            out = rgb - albedo / pi * (irr - _floor0(irr - lost))
     for k in range(F.shape[0]):
         out = out + (albedo / pi * F[k][..., None] + R[k][..., None]) * _colour(colours[k], rgb)
     if G is not None:

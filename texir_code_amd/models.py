@@ -109,6 +109,32 @@ def irt_light_bounce_settings(conf, lights, default_samples):
     return n, albedo, s
 
 
+def irt_light_shadow_settings(conf, default_samples):
+    """the optional keys of the inserted emitters' body shadow (Scene.irt_shadow), used only when train.irt_lights names lights:
+      train.irt_light_shadow = false (default: no shadow files) | true: what every lamp's body, and all of them together, take from the irradiance;
+      train.irt_light_shadow_samples = samples per texel (default: the stage's own sample count -- the shadow is a part of THAT estimate).
+    -> (on, samples); bad values raise ValueError"""
+    on = conf.get("train.irt_light_shadow", False)
+    if not isinstance(on, bool):
+        raise ValueError("train.irt_light_shadow must be true or false, got %r" % (on,))
+    s = conf.get("train.irt_light_shadow_samples", default_samples)
+    try:
+        if isinstance(s, bool) or int(s) != float(s) or int(s) < 1:
+            raise ValueError
+        s = int(s)
+    except (TypeError, ValueError):
+        raise ValueError("train.irt_light_shadow_samples must be an integer >= 1, got %r" % (s,))
+    return on, s
+
+
+def light_shadow_sets(K):
+    """the sets the stage asks Scene.irt_shadow for, as calls of at most 8 sets: one set per lamp, and for K > 1 the union of all -- one call when
+    K + 1 <= 8, else two"""
+    singles = [[k] for k in range(K)]
+    union = [list(range(K))] if K > 1 else []
+    return [singles + union] if K + len(union) <= 8 else [singles, union]
+
+
 def load_albedo_image(spec):
     """train.irt_light_albedo -> float32 [Ha,Wa,3] in file orientation: one float (a 1 x 1 image: every resize of it is that constant), an .hdr, or a
     .png (8 / 16 bit, scaled to 0..1)"""
@@ -217,6 +243,10 @@ class TracerO3d(nn.Module):
         # diffuse bounces of the inserted emitters' light (irtlight.bounce: Scene.irt_multi, all lights in one traced pass per bounce)
         self.irt_light_bounces, self.irt_light_albedo, self.irt_light_bounce_samples = irt_light_bounce_settings(conf, self.irt_lights, int(self.sample_l[0]))
         self.ir_lights_bounce = None
+        # train.irt_light_shadow / irt_light_shadow_samples (optional keys, irt_light_shadow_settings above): forward() also traces what the lamps' bodies
+        # take from the irradiance (Scene.irt_shadow): ir_lights_shadow [K,H,W,3] per lamp and, for K > 1, ir_lights_shadow_all [H,W,3] for all together
+        self.irt_light_shadow, self.irt_light_shadow_samples = irt_light_shadow_settings(conf, int(self.sample_l[0]))
+        self.ir_lights_shadow = self.ir_lights_shadow_all = None
         # optional exact texel G-buffer written by the synthetic generator (bypasses the panorama gather)
         self.texel_gbuffer_path = _sibling(self.path_traced_mesh, "texel_gbuffer.npz")
 
@@ -357,6 +387,13 @@ class TracerO3d(nn.Module):
                         src = texpost.pad_texture((~seam).reshape(H, W, 1).to(torch.float32), return_src=True)[1]
                     self.ir_lights_bounce = irtlight.bounce(self.scene, pos, nrm, shift, albedo, self.ir_lights, self.irt_light_bounce_samples,
                                                             bounces=self.irt_light_bounces, texel_ids=ids, hw=(H, W), src=src).reshape(-1, H, W, 3)
+            if self.irt_light_shadow:
+                with phases.phase("irt_light_shadow"):
+                    bodies = torch.from_numpy(records).to(self.device)
+                    lost = torch.cat([self.scene.irt_shadow(pos, nrm, shift, self.irt_light_shadow_samples, bodies, sets=sets, mode=self.sample_type[0], texel_ids=ids)
+                                      for sets in light_shadow_sets(records.shape[0])]).reshape(-1, H, W, 3)
+                    self.ir_lights_shadow = lost[:records.shape[0]]
+                    self.ir_lights_shadow_all = lost[records.shape[0]] if lost.shape[0] > records.shape[0] else None
         self.ir_texture = irr.reshape(H, W, 3)
         return self.ir_texture
 

@@ -276,6 +276,67 @@ class Scene:
                                          K, _lib.ptr(out) if K else None, _lib.ptr(ws), ws_bytes, _lib.stream_ptr()))
         return out
 
+    # -- the shadow of inserted emitters' bodies on the captured light (include/texir_hip.h texir_irt_shadow) --
+    def irt_shadow(self, pos, nrm, shift, n_samples, bodies, sets=None, mode="uniform", texel_ids=None, out=None, stats=False, max_workspace_bytes=4 << 30):
+        """what the bodies of inserted emitters take from the captured irradiance: bodies [K,16] float32 records (irtlight.pack; a device tensor is used
+        in place, so a recorded graph replays with whatever the records hold then), K <= 8; sets: M <= 8 lists of body indices (default: one set per
+        body, [[0], [1], ...]), or a uint32-valued integer tensor of M bit masks, used in place when it is an int32 device tensor -> lost [M, Nt, 3]:
+        lost[m] is the part of irt_generate's irradiance that arrived along rays a body of set m now intercepts (a union over the set, not a sum), so the
+        relit irradiance is max(E - lost[m], 0) + the lights' own terms (irtlight.add(..., lost=)).  Any point list: texels or a view's pixels.  The id
+        list is walked in slices that are multiples of 64 texels so that the partial-sum workspace stays under max_workspace_bytes; the cuts do not
+        change a bit.  Only listed texels are written.  stats=True: also int64 [2] = (samples whose ray met a body: the rays traced, blocked ones)"""
+        pos = _dev_f32(pos, self.device).reshape(-1, 3)
+        nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
+        Nt = pos.shape[0]
+        shift = _dev_f32(shift, self.device).reshape(Nt, 2)
+        N = int(n_samples)
+        bodies = _dev_f32(bodies, self.device)
+        if bodies.ndim != 2 or bodies.shape[1] != 16:
+            raise ValueError("bodies must be [K,16], got %r" % (tuple(bodies.shape),))
+        K = int(bodies.shape[0])
+        if sets is None:
+            sets = [[k] for k in range(K)]
+        if torch.is_tensor(sets):
+            masks = sets.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        else:
+            bits = []
+            for m, members in enumerate(sets):
+                v = 0
+                for k in members:
+                    if not 0 <= int(k) < 32:
+                        raise ValueError("set %d names body %r: indices are 0..31 (bits at or above K are ignored)" % (m, k))
+                    v |= 1 << int(k)
+                bits.append(v - (1 << 32) if v >= 1 << 31 else v)
+            masks = torch.tensor(bits, dtype=torch.int32).reshape(-1).to(self.device)
+        M = int(masks.numel())
+        if out is None:
+            out = torch.zeros((M, Nt, 3), device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (M, Nt, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float32 [%d,%d,3] on %s" % (M, Nt, self.device))
+        st = torch.zeros(2, device=self.device, dtype=torch.int64) if stats else None
+        ids = None
+        n = Nt
+        if texel_ids is not None:
+            ids = texel_ids.to(device=self.device, dtype=torch.int32).contiguous()
+            n = ids.numel()
+        if n == 0:
+            return (out, st) if stats else out
+        L = _lib.lib()
+        per_texel = int(L.texir_irt_shadow_workspace_bytes(1, N, M))      # (0 for arguments the library refuses: the call below then reports them)
+        step = n
+        if per_texel > 0 and per_texel * n > int(max_workspace_bytes):
+            step = max(64, int(max_workspace_bytes) // per_texel // 64 * 64)
+            if ids is None:
+                ids = torch.arange(Nt, device=self.device, dtype=torch.int32)
+        ws_bytes = max(per_texel * step, 16)
+        ws = torch.empty(ws_bytes, device=self.device, dtype=torch.uint8)
+        for first in range(0, n, step):
+            cnt = min(step, n - first)
+            part = None if ids is None else ids[first:first + cnt]
+            _lib.check(L.texir_irt_shadow(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(part), cnt, Nt, N, MODES[mode], _lib.ptr(bodies) if K else None,
+                                          K, _lib.ptr(masks) if M else None, M, _lib.ptr(out) if M else None, _lib.ptr(st), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()))
+        return (out, st) if stats else out
+
     # -- inserted emitters (include/texir_hip.h texir_irt_lights) ------------------------------------------
     def irt_lights(self, pos, nrm, shift, lights, n_samples, texel_ids=None, t_max=0.999, out=None, stats=False, query="closest"):
         """direct irradiance factors of inserted area lights: lights [K,16] float32 records (irtlight.pack; a device tensor is used in place, so a

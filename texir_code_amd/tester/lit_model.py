@@ -4,13 +4,18 @@
     test.light_samples = 64
     test.light_bounces = 0            diffuse bounces of the new light (irtlight.bounce), gathered once at construction on the irradiance texture's grid
     test.light_bounce_samples = 256   samples per texel and bounce
+    test.light_shadows = false        the shadow the lamps' bodies cast on the captured diffuse light (Scene.irt_shadow), traced once at construction
+    test.light_shadow_samples = 256   samples per texel
 
 With lights, render() adds their diffuse and specular response to every rendered view, sum_k colour_k (albedo / pi F[k] + R[k]) (Scene.irt_lights,
 Scene.spec_lights, irtlight.add_view), at test.light_samples samples per pixel, light and technique, with the pixels' own specular shift and the model's
 floor of denominators.  With test.light_bounces >= 1 the model also builds, once, a texel G-buffer of irt.hdr's size, the lights' factors F per texel, and
 G = irtlight.bounce(...) with the albedo texture as the diffuse albedo; it keeps sum_k colour_k G[k] as a texture in file orientation, forward() fetches
 it with the very call that fetches the irradiance texture, and render() adds albedo / pi times that.  The texel shifts come from a private generator with a
-fixed seed: the CPU generator's stream stays what it is.  Not computed: the shadow an emitter's body casts on the captured light, a specular bounce.
+fixed seed: the CPU generator's stream stays what it is.  With test.light_shadows the model builds, once and on the same texel G-buffer with the same
+private generator, `lost`: what the union of the lamps' bodies takes from the captured irradiance; forward() fetches it like the irradiance texture and
+render() takes albedo / pi * (irr - max(irr - lost, 0)) from the diffuse term before the lamps' light is added (irtlight.add_view(lost=, irr=)).
+Not computed: the bodies' shadow in the specular term of captured light, bodies shadowing each other's light, the body drawn in the view, a specular bounce.
 With the default `none` the class IS its base: every file Editing, View, Relighting and Error write is unchanged byte for byte.
 This is the class the plugin registry hands the tester runners for models.test_nvdiffrast.MaterialModel."""
 import torch
@@ -44,6 +49,20 @@ def light_bounce_settings(conf):
     return tuple(out)
 
 
+def light_shadow_settings(conf):
+    """test.light_shadows (false) and test.light_shadow_samples (256) -> (on, samples >= 1); bad values raise ValueError"""
+    on = conf.get("test.light_shadows", False)
+    if not isinstance(on, bool):
+        raise ValueError("test.light_shadows must be true or false, got %r" % (on,))
+    v = conf.get("test.light_shadow_samples", 256)
+    try:
+        if isinstance(v, bool) or int(v) != float(v) or int(v) < 1:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("test.light_shadow_samples must be an integer >= 1, got %r" % (v,))
+    return on, int(v)
+
+
 class MaterialModel(TM.MaterialModel):
     def __init__(self, conf, *args, **kwargs):
         super().__init__(conf, *args, **kwargs)
@@ -51,19 +70,36 @@ class MaterialModel(TM.MaterialModel):
         self.light_samples = int(conf.get("test.light_samples", 64))
         self.light_bounces, self.light_bounce_samples = light_bounce_settings(conf)
         self.bounce_tex = None
+        self.light_shadows, self.light_shadow_samples = light_shadow_settings(conf)
+        self.shadow_tex = None
         if self.test_lights is not None and self.light_bounces >= 1:
             self.build_bounce_texture()
+        if self.test_lights is not None and self.light_shadows:
+            self.build_shadow_texture()
 
-    def build_bounce_texture(self):
-        """sum_k colour_k G[k] on the irradiance texture's grid, file orientation -> self.bounce_tex [H,W,3] (device)"""
-        records, colours = self.test_lights
+    def _texel_inputs(self):
+        """the texel G-buffer of the irradiance texture's grid and the texel shifts of the private generator: (H, W, pos, nrm, shift, ids, covered)"""
         H, W = int(self.irrt.shape[0]), int(self.irrt.shape[1])
         pos, nrm, prim, _ = GB.raster_texel_gbuffer(self.scene, H, W, normal="geometric", offset=1e-2, want_ids=True)
         covered = (prim >= 0).reshape(-1)
         ids = torch.nonzero(covered)[:, 0].to(torch.int32)
         gen = torch.Generator().manual_seed(BOUNCE_SEED)
         shift = torch.rand(H * W, 2, generator=gen).to(self.device)
-        pos, nrm = pos.reshape(-1, 3).contiguous(), nrm.reshape(-1, 3).contiguous()
+        return H, W, pos.reshape(-1, 3).contiguous(), nrm.reshape(-1, 3).contiguous(), shift, ids, covered
+
+    def build_shadow_texture(self):
+        """what the union of the lamps' bodies takes from the captured irradiance, on the irradiance texture's grid, file orientation
+        -> self.shadow_tex [H,W,3] (device)"""
+        records, _ = self.test_lights
+        H, W, pos, nrm, shift, ids, _ = self._texel_inputs()
+        lost = self.scene.irt_shadow(pos, nrm, shift, int(self.light_shadow_samples), records, sets=[list(range(records.shape[0]))], texel_ids=ids)
+        self.shadow_tex = lost[0].reshape(H, W, 3).contiguous()
+        return self.shadow_tex
+
+    def build_bounce_texture(self):
+        """sum_k colour_k G[k] on the irradiance texture's grid, file orientation -> self.bounce_tex [H,W,3] (device)"""
+        records, colours = self.test_lights
+        H, W, pos, nrm, shift, ids, covered = self._texel_inputs()
         F = self.scene.irt_lights(pos, nrm, shift, records, int(self.light_samples), texel_ids=ids).reshape(-1, H, W)
         src = None
         if (H, W) == tuple(self.scene.tex_shape[:2]):
@@ -75,15 +111,18 @@ class MaterialModel(TM.MaterialModel):
         return self.bounce_tex
 
     def forward(self, mvp, id, cam_position, *args, **kwargs):
-        tex = getattr(self, "bounce_tex", None)
-        if tex is None:
+        tex, sh = getattr(self, "bounce_tex", None), getattr(self, "shadow_tex", None)
+        if tex is None and sh is None:
             return super().forward(mvp, id, cam_position, *args, **kwargs)
         gb = self._gbuffer(mvp, id)                                          # (cached: the base's own call below gets the same G-buffer)
-        self._bounce_irr = tex_fetch(tex, gb["uv"], gb["uv_da"], "linear-mipmap-linear", self.max_mip_level)
+        if tex is not None:
+            self._bounce_irr = tex_fetch(tex, gb["uv"], gb["uv_da"], "linear-mipmap-linear", self.max_mip_level)
+        if sh is not None:
+            self._shadow_irr = tex_fetch(sh, gb["uv"], gb["uv_da"], "linear-mipmap-linear", self.max_mip_level)
         try:
             return super().forward(mvp, id, cam_position, *args, **kwargs)
         finally:
-            self._bounce_irr = None
+            self._bounce_irr = self._shadow_irr = None
 
     def render(self, normal, albedo, roughness, points, cam_position, irr):
         lights = getattr(self, "test_lights", None)
@@ -104,6 +143,10 @@ class MaterialModel(TM.MaterialModel):
         pts, nrm, alb = points.reshape(P, 3), normal.reshape(P, 3), albedo.reshape(P, 3)
         F = self.scene.irt_lights(pts, nrm, shift_s, records, n_l)
         R = self.scene.spec_lights(pts, nrm, roughness.reshape(P), shift_s, cam_position, records, n_l, clamp_eps=TM.TINY_NUMBER)
-        G = getattr(self, "_bounce_irr", None)
-        res["rgb"] = irtlight.add_view(res["rgb"].reshape(P, 3), alb, F, R, colours, G=None if G is None else G.reshape(P, 3)).reshape(shape + (3,))
+        G, lost = getattr(self, "_bounce_irr", None), getattr(self, "_shadow_irr", None)
+        if lost is None:
+            res["rgb"] = irtlight.add_view(res["rgb"].reshape(P, 3), alb, F, R, colours, G=None if G is None else G.reshape(P, 3)).reshape(shape + (3,))
+        else:
+            res["rgb"] = irtlight.add_view(res["rgb"].reshape(P, 3), alb, F, R, colours, G=None if G is None else G.reshape(P, 3), lost=lost.reshape(P, 3),
+                                           irr=irr.reshape(P, 3)).reshape(shape + (3,))
         return res

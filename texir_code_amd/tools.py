@@ -47,13 +47,15 @@ From the files an IrT stage with train.irt_split wrote into <dir> (0_irr_texture
 class off).  --replace: class k's texels become ONE colour instead, colour * 0_irr_texture_unit<k>.hdr (train.irt_split_unit; the reference's "lamp texels
 become one colour", models/test_nvdiffrast.py:109-110).  Irradiance is linear in the radiance texture: nothing is traced.  Existing files are not overwritten.
 
-    python -m texir_code_amd.tools light-irt <dir> --light k --colour r,g,b [--light j --colour r,g,b ...] [--base <file>] [--bounce]
+    python -m texir_code_amd.tools light-irt <dir> --light k --colour r,g,b [--light j --colour r,g,b ...] [--base <file>] [--bounce] [--shadow]
 
 From the files an IrT stage with train.irt_lights wrote into <dir> (0_irr_texture_light<k>.hdr, the irradiance under inserted emitter k at unit radiance):
 0_irr_texture_lit.hdr = base + sum colour_k * 0_irr_texture_light<k>.hdr -- the listed emitters switched on at those radiances.  Direct light only,
 unless --bounce: then colour_k * 0_irr_texture_light<k>_bounce.hdr (train.irt_light_bounces: the new light's diffuse bounces) is added for every named
 light as well.  The base is <dir>/0_irr_texture.hdr, or --base <file>, e.g. a 0_irr_texture_relit.hdr from relight-irt.  Irradiance is linear in emitted radiance: nothing is
-traced.  Existing files are not overwritten.
+traced.  --shadow: what the lamps' BODIES take from the base is subtracted first, floored at zero (train.irt_light_shadow: 0_irr_texture_lights_shadow.hdr, the
+union of all bodies, when every light of the directory is named; 0_irr_texture_light<k>_shadow.hdr when one light is named; no other subset has a file).
+Existing files are not overwritten.
 """
 import sys
 
@@ -200,9 +202,9 @@ def relight_irt(directory, k, colour, replace=False):
     return dst
 
 
-def light_irt(directory, lights, base=None, bounce=False):
-    """lights: [(k, (r, g, b)), ...]; bounce: also the lights' bounce files -> the path written.  FileExistsError / FileNotFoundError / ValueError name
-    what is wrong"""
+def light_irt(directory, lights, base=None, bounce=False, shadow=False):
+    """lights: [(k, (r, g, b)), ...]; bounce: also the lights' bounce files; shadow: the bodies' shadow on the base first -> the path written.
+    FileExistsError / FileNotFoundError / ValueError name what is wrong"""
     import os
     from . import irtlight
     dst = os.path.join(directory, "0_irr_texture_lit.hdr")
@@ -223,7 +225,25 @@ def light_irt(directory, lights, base=None, bounce=False):
         if img.shape != E.shape:
             raise ValueError("%s is %r, the base %s is %r" % (f, img.shape, base, E.shape))
         F.append(img[..., 0])
-    out = irtlight.add(E, np.stack(F), [c for _, c in lights])
+    lost = None
+    if shadow:
+        import re
+        named = sorted(set(k for k, _ in lights))
+        have = sorted(int(m.group(1)) for m in (re.fullmatch(r"0_irr_texture_light(\d+)\.hdr", n) for n in os.listdir(directory)) if m)
+        if len(named) == 1:
+            f = os.path.join(directory, "0_irr_texture_light%d_shadow.hdr" % named[0])
+        elif named == have:
+            f = os.path.join(directory, "0_irr_texture_lights_shadow.hdr")
+        else:
+            raise FileNotFoundError("--shadow of the lights %s: the stage writes the shadow of one lamp (0_irr_texture_light<k>_shadow.hdr) and of all %d "
+                                    "together (0_irr_texture_lights_shadow.hdr), no other subset: name one light or all (train.irt_light_shadow = true)"
+                                    % (named, len(have)))
+        if not os.path.exists(f):
+            raise FileNotFoundError("--shadow needs %s: run the IrT stage with train.irt_light_shadow = true (and train.irt_lights)" % f)
+        lost = np.asarray(IO.read_hdr(f), np.float32)
+        if lost.shape != E.shape:
+            raise ValueError("%s is %r, the base %s is %r" % (f, lost.shape, base, E.shape))
+    out = irtlight.add(E, np.stack(F), [c for _, c in lights], lost=lost)
     if bounce:
         G = []
         for k, _ in lights:
@@ -241,7 +261,7 @@ def light_irt(directory, lights, base=None, bounce=False):
 
 def main(argv):
     if len(argv) >= 2 and argv[0] == "light-irt":
-        rest, lights, base, bad, bounce = [], [], None, False, False
+        rest, lights, base, bad, bounce, shadow = [], [], None, False, False, False
         it = iter(argv[1:])
         for a in it:
             key, eq, val = a.partition("=")
@@ -263,15 +283,17 @@ def main(argv):
                     bad = True
             elif a == "--bounce":
                 bounce = True
+            elif a == "--shadow":
+                shadow = True
             elif a.startswith("--"):
                 bad = True
             else:
                 rest.append(a)
         if bad or len(rest) != 1 or not lights or any(c is None for _, c in lights):
-            print("light-irt needs <dir> --light k --colour r,g,b [--light k --colour r,g,b ...] [--base <file>] [--bounce]")
+            print("light-irt needs <dir> --light k --colour r,g,b [--light k --colour r,g,b ...] [--base <file>] [--bounce] [--shadow]")
             return 2
         try:
-            dst = light_irt(rest[0], [(k, c) for k, c in lights], base, bounce)
+            dst = light_irt(rest[0], [(k, c) for k, c in lights], base, bounce, shadow)
         except (FileExistsError, FileNotFoundError) as e:
             print(e)
             return 1

@@ -101,6 +101,14 @@ class IrrTextureRunner:
                 with phases.phase("write_hdr", sync=False):
                     for k in range(bounce.shape[0]):
                         IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_light%d_bounce.hdr" % k), bounce[k].contiguous().cpu().numpy())
+            # train.irt_light_shadow (models.TracerO3d): what every inserted emitter's body takes from the irradiance, and all of them together
+            shadow, shadow_all = getattr(self.model, "ir_lights_shadow", None), getattr(self.model, "ir_lights_shadow_all", None)
+            if shadow is not None:
+                with phases.phase("write_hdr", sync=False):
+                    for k in range(shadow.shape[0]):
+                        IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_light%d_shadow.hdr" % k), shadow[k].contiguous().cpu().numpy())
+                    if shadow_all is not None:
+                        IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_lights_shadow.hdr"), shadow_all.contiguous().cpu().numpy())
         return irr_texture
 
     def _write_irt(self, irr_texture, path):
