@@ -70,6 +70,9 @@ TEXIR_API int texir_scene_set_texture(texir_scene* scene, const float* tex, int3
  * older A/B layouts).  Decided at texir_scene_create and again at every texir_scene_set_texture (which then synchronises `stream` once to read the
  * pack kernel's verdict; on a capturing stream the float32 layout is taken).  Results are bit-identical in every layout. */
 TEXIR_API int texir_scene_texture_layout(const texir_scene* scene, int32_t* layout);
+/* The axis-aligned box of the vertices the scene's triangles name, out /+host+/ = (lo.x, lo.y, lo.z, hi.x, hi.y, hi.z): exact float32 minima and maxima of
+ * the coordinates texir_scene_create was given (what texir_irt_shadow_mesh's prefilter pads). */
+TEXIR_API int texir_scene_bounds(const texir_scene* scene, float out[6]);
 /* Host statement of the 4-byte texel: word = m_r | m_g << 8 | m_b << 16 | E << 24, value_c = m_c * 2^(E - 127).  rgb /+host+/ [n,3] f32 ->
  * words /+host+/ [n], exact /+host+/ [n] (nullable; 1 where the triple has this form: non-negative, finite, normal, one shared power of two with
  * 8-bit integers -- e.g. any cv2-decoded RGBE pixel times 2^k; 0 -> the word is 0 and the device keeps float32 texels).  unpack is the decode. */
@@ -296,6 +299,74 @@ TEXIR_API int texir_irt_shadow(const texir_scene* scene, const float* pos /*dev*
                        const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode, const float* bodies /*dev [K][16]*/,
                        int32_t K /*0..8*/, const uint32_t* sets /*dev [M]*/, int32_t M /*1..8*/, float* out /*dev [M][Nt][3]*/,
                        uint64_t* stats /*dev [2], nullable*/, void* workspace /*dev*/, int64_t workspace_bytes, void* stream);
+
+/* ---- the shadow an inserted triangle-mesh OBJECT casts on the captured light, per texel (csrc/irtshadowmesh.hip): texir_irt_shadow with meshes in the place
+ * of analytic bodies -- a chair, a table, a person placed into the captured room.
+ *
+ * THE RULE.  Inputs: everything texir_irt_generate takes, and
+ *   occluders   Q in 0..8 scene handles (HOST array) used for their geometry only: build one with texir_scene_create, any uvs and a 1 x 1 texture.  Their
+ *               device pointers and boxes enter the kernel arguments by value: fixed when the call is made or recorded.
+ *   instances   K in 0..8: instance j = (inst_obj[j] in 0..Q-1, HOST; W[j] = inst_world_to_obj + 12 j, a WORLD-TO-OBJECT 3 x 4 row-major float32 matrix in
+ *               DEVICE memory: a replayed graph sees a moved object, so the host never reads a matrix).  Two instances may name one occluder.
+ *   sets        M in 1..8 uint32 bit masks over the instances in DEVICE memory, exactly as texir_irt_shadow's: bits at or above K are ignored, a zero mask
+ *               yields zeros.
+ *   SAMPLES AND RAYS  directions d, ndl from the RAW normal, the ray (x = pos, d), the closest hit t_s and its acceptance test (slot >= 0 && t > 1e-4) are
+ *               those of irt_group_kernel<false, 4, 6>; L_i comes from the scene's OWN texture through the hit shader.
+ *   OBJECT-SPACE RAY of instance j, a FLOAT32 OPERATION SEQUENCE (each operation separately rounded, no contraction), r = 0, 1, 2, W = W[j]:
+ *               o'_r = ((W[r][0] x_0 + W[r][1] x_1) + W[r][2] x_2) + W[r][3]
+ *               d'_r =  (W[r][0] d_0 + W[r][1] d_1) + W[r][2] d_2
+ *               The ray is NOT normalised: an affine map keeps the ray parameter, t along (o', d') is t along (x, d).  A matrix with a non-finite entry
+ *               never blocks.
+ *   BLOCKED     sample i with an accepted scene hit at t_s is blocked by instance j iff the occluder's tree holds a triangle the closest-hit query's leaf test
+ *               accepts with 0 < t < t_s along (o', d'), t the float32 t that test computes: texir_trace_occluded's rule at t_near = 0, t_far = t_s, which
+ *               is the bit `closest hit of (o', d') in the occluder has t < t_s`.  B_i = the mask of instances that block sample i.
+ *   RESULT      lost[m] = (2 pi / N) sum_i L_i ndl_i [sample i has an accepted hit AND (sets[m] & B_i) != 0]: overlapping instances are a union, not a sum.
+ *   REDUCTION   texir_irt_shadow's: acc_m += L ndl per lane over the passes of a part in irt_group_kernel's pass order; partial[part][m][i][3]; parts (those
+ *               of the 64-texel plan under TEXIR_IRT_MIN_PART_CELLS, TEXIR_IRT_LOG2PARTS) added in part order; out[m][t][c] = ((a * 2) * pi) / N.
+ *   CONSEQUENCE where every accepted sample of a texel is blocked under set m, lost[m] is bit for bit texir_irt_generate's 64-texel form; where none is, it is
+ *               exactly +0.  List order, duplicates, list cuts, launch shape, stream, graph replay and the prefilter (below) change no bit.
+ * ROUNDING BOUND (first order, u = 2^-24; x and W are exact float32 values, d_i carries e_i per component; the tests multiply by their factor K).  o' uses IEEE
+ * products and sums of exact float32 values only: a restatement on any IEEE machine gives the same bits, and the bound starts from o' as an exact value.
+ *               |dd'_r| <= sum_c |W[r][c]| e_c + 3 u sum_c |W[r][c] d_c|
+ *   The traversal then sees (o', d' +- dd'): a triangle's t carries the closest-hit query's own bound_t for that direction bound (tests/trace_cases.py), and
+ *   BLOCKED is decided unless |t_o - t_s| <= bound_t(t_o) + bound_t(t_s) or the triangle is within its margin of the ray.
+ *
+ * PREFILTER.  A lane queries instance j only if (o', d') passes a test against the occluder's object-space box (texir_scene_bounds), a lane that passes for no
+ * instance does not trace the scene either, and a pass no lane needs is skipped.  The test must never fail where the traversal accepts a triangle:
+ *   what is to be covered.  The tree's boxes -- quantised or float, each padded OUTWARDS by the builder's slack -- only ever REJECT: the traversal accepts a subset
+ *   of what the leaf test accepts over all triangles, so it suffices to cover the leaf test (device_common.h).  With kz the dominant axis of d', S = (d'_k1 rcp
+ *   d'_kz, d'_k2 rcp d'_kz) (each at most 2.5 u off, |S| <= 1 + 3 u), q = fl(p - o') per corner p and X = fl(q_k1 - S_x q_kz), Y alike: the test accepts only if
+ *   the 2D origin lies in the triangle (X, Y) -- signs exact (edge2_exact) -- and the computed t > 0.  (X, Y) is the EXACT shear along D = (S_x, S_y, 1) of corners
+ *   moved by at most u |p - o'| (q) + 2.01 u |q| (X, Y) <= 3.1 u R per axis, R = max_corner |p - o'|_inf <= rb + |o'|_inf, rb = the box's largest |coordinate|.
+ *   So the line o' + s D meets the moved triangle at some |s| <= (1 + 3.1 u) R, and the line o' + t d' passes within 3.1 u R + 2.6 u R < 6 u R of the true
+ *   triangle, per axis.  The computed t is sum U_k Z_k / det with the U_k of one sign and Z_k = fl(rcp(d'_kz) q_k,kz): t > 0 needs some Z_k > 0, i.e. a corner
+ *   with (p - o')_kz d'_kz > 0, the sign of a float32 difference being exact.  (The weights U_k may be badly off under cancellation, so nothing is claimed about
+ *   WHERE along the line the hit lies.)
+ *   the test.   P = 2^-18 (rb + |o'|_inf) + 1e-30 = 64 u R and more; box' = box padded by P (its roundings, and that of box' - o', at most 3 u R, are inside).
+ *   (1) a zero or non-finite d' passes; (2) along kz -- picked by the traversal's own comparisons -- the far plane must lie strictly ahead: d'_kz > 0 ?
+ *   hi'_kz > o'_kz : lo'_kz < o'_kz; (3) the LINE must meet box': per axis with d'_r = 0, lo'_r <= o'_r <= hi'_r; else i = rcp(d'_r) (within 1 ulp), a = (lo'_r - o'_r) i, b =
+ *   (hi'_r - o'_r) i, the smaller moved down and the larger moved up by 2^-21 of itself (8 u against the 2.5 u of reciprocal and product), tn = max, tf = min
+ *   over the axes starting from -inf, +inf; a distance that is not a number narrows nothing; pass iff not tn > tf.  (2) and (3) hold for every accepted triangle
+ *   by the paragraph above, with a tenfold margin in P.  flags bit 0 switches the test off (every lane queries every valid instance): the results must not
+ *   change by a bit, which is how the tests hold this argument.
+ *
+ *   out [M][Nt][3] dev: only listed texels are written, zeros included (K = 0: zeros).  texel_ids NULL => all Nt (n_ids ignored); a non-null list with
+ *   n_ids == 0 is a no-op.
+ *   stats dev u64[3], nullable: += samples whose ray met some box (= the scene rays traced), occluder queries issued, blocked samples (an accepted hit behind an
+ *   instance, of any set or none); one atomic add per wave and counter.  With the prefilter off every sample of a live texel counts as met.
+ *   workspace: texir_irt_shadow_mesh_workspace_bytes(n_ids, N, M) bytes of device scratch (12 bytes x M x parts per listed texel; 0 for refused arguments).
+ * Caller-owned buffers, the caller's stream, no allocation, no synchronisation, no atomics on results: the call records into a hipGraph.  Q or K outside 0..8,
+ * M outside 1..8, inst_obj[j] outside 0..Q-1, N < 1 (all reported before any null buffer), a null buffer, a workspace that is too small, the scene or an
+ * occluder without the 4-wide tree and an occluder on another device than the scene are errors with a texir_last_error() text.
+ * Not computed here: objects shadowing the inserted emitters' F, R or G; a union with analytic bodies in one call (the two lost terms double-count where they
+ * overlap); the object's shadow in the specular term; the object drawn in a view; more than 8 occluders, instances or sets per call. */
+TEXIR_API int64_t texir_irt_shadow_mesh_workspace_bytes(int64_t n_ids, int32_t N, int32_t M);
+TEXIR_API int texir_irt_shadow_mesh(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const float* shift /*dev*/,
+                       const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode,
+                       const texir_scene* const* occluders /*host [Q]*/, int32_t Q /*0..8*/, const int32_t* inst_obj /*host [K]*/,
+                       const float* inst_world_to_obj /*dev [K][12]*/, int32_t K /*0..8*/, const uint32_t* sets /*dev [M]*/, int32_t M /*1..8*/,
+                       float* out /*dev [M][Nt][3]*/, uint64_t* stats /*dev [3], nullable*/, uint32_t flags /*bit 0: prefilter off*/, void* workspace /*dev*/,
+                       int64_t workspace_bytes, void* stream);
 
 /* name of the kernel form ONE texir_irt_generate call over n_ids listed texels at N samples launches on this scene
  * ("irt_group_kernel<false, 4, 6>": 64 texels per wave; "irt_kernel<false, 4|2>": one texel per wave) -- the launcher's own

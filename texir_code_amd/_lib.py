@@ -36,6 +36,7 @@ def signatures():
         "texir_scene_destroy": [vp],
         "texir_scene_set_texture": [vp, vp, i32, i32, i32, vp],
         "texir_scene_texture_layout": [vp, vp],
+        "texir_scene_bounds": [vp, vp],
         "texir_texel_pack": [vp, i64, vp, vp],
         "texir_texel_unpack": [vp, i64, vp],
         "texir_scene_info": [vp, vp],
@@ -53,6 +54,8 @@ def signatures():
         "texir_irt_multi": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, vp, vp, i64, vp],
         "texir_irt_shadow_workspace_bytes": (i64, [i64, i32, i32]),
         "texir_irt_shadow": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, vp, i32, vp, vp, vp, i64, vp],
+        "texir_irt_shadow_mesh_workspace_bytes": (i64, [i64, i32, i32]),
+        "texir_irt_shadow_mesh": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, C.c_uint32, vp, i64, vp],
         "texir_irt_kernel_name": [vp, i64, i32, text, i32],
         "texir_spec_forward": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp],
         "texir_spec_forward_train": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp, vp],

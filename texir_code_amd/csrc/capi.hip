@@ -31,6 +31,7 @@ struct texir_scene {
     unsigned int* d_tex_flag = nullptr;  // device word: texels of the last pack that were not representable
     int64_t n_nodes = 0, n_nodes4 = 0, n_tris = 0, n_slots = 0 /* leaf-order slots behind d_tris / d_uvs / d_cnrm: 2 per quad record (bvh_build.h) */, n_quads = 0, n_uv_recs = 0 /* 32-byte uv records behind d_uvs: one per quad record */, max_depth = 0;
     int width = 2;
+    float bounds[6] = {0, 0, 0, 0, 0, 0};   // (lo.x, lo.y, lo.z, hi.x, hi.y, hi.z) of the vertices the triangles name (texir_scene_bounds)
     size_t tex_bytes = 0;
     std::vector<uint32_t> slot_prim;     // leaf slot -> primitive id (host copy, for per-corner attribute uploads; 0xFFFFFFFF: an empty slot)
     std::vector<uint8_t> slot_rot;       // leaf slot -> rotation of the stored corners (stored corner k = the caller's corner (rot + k) % 3)
@@ -228,6 +229,13 @@ int texir_scene_create(const float* verts, int32_t V, const int32_t* tris, int32
     s->slot_prim.resize((size_t)h.n_slots); s->slot_rot.resize((size_t)h.n_slots);
     for (int64_t i = 0; i < h.n_slots; i++) { s->slot_prim[i] = h.tris[i].prim; uint32_t r; std::memcpy(&r, &h.tris[i].pad1, 4); s->slot_rot[i] = (uint8_t)(r % 3u); }
     s->device = device; s->n_nodes = (int64_t)h.nodes.size(); s->n_tris = T; s->max_depth = h.max_depth;
+    for (int a = 0; a < 3; a++) { s->bounds[a] = verts[3 * (size_t)tris[0] + a]; s->bounds[3 + a] = s->bounds[a]; }
+    for (int64_t i = 0; i < 3 * (int64_t)T; i++)
+        for (int a = 0; a < 3; a++) {
+            const float v = verts[3 * (size_t)tris[i] + a];
+            if (v < s->bounds[a]) s->bounds[a] = v;
+            if (v > s->bounds[3 + a]) s->bounds[3 + a] = v;
+        }
     s->tex_bytes = sizeof(float) * 3 * (size_t)Ht * Wt;
     auto bail = [&](hipError_t e, const char* what) { texir_scene_destroy(s); return fail(TEXIR_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); };
     // one device buffer of the scene: allocated and, where there is a host source, filled
@@ -289,6 +297,13 @@ int texir_scene_info(const texir_scene* s, int64_t out[8])
     out[0] = s->width == 4 ? s->n_nodes4 : s->n_nodes; out[1] = s->n_tris; out[2] = s->max_depth;
     out[3] = s->width == 4 ? s->n_nodes4 * (int64_t)(sizeof(GpuNode4) + (s->d_nodes4f ? sizeof(GpuNode4F) : 0)) : s->n_nodes * (int64_t)sizeof(GpuNode);
     out[4] = s->n_slots * (int64_t)sizeof(GpuTri) + s->n_quads * (int64_t)sizeof(GpuQuad); out[5] = s->d_uvs ? s->n_uv_recs * (int64_t)sizeof(GpuTriUV) : 0; out[6] = (int64_t)(s->dev.tex_layout >= 3 ? s->packed_bytes : s->dev.tex_layout >= 1 ? s->tiled_bytes : s->tex_bytes); out[7] = s->device;
+    return TEXIR_OK;
+}
+
+int texir_scene_bounds(const texir_scene* s, float out[6])
+{
+    if (!s || !out) return fail(TEXIR_ERR_INVALID, "texir_scene_bounds: null argument");
+    for (int a = 0; a < 6; a++) out[a] = s->bounds[a];
     return TEXIR_OK;
 }
 
@@ -521,6 +536,54 @@ int texir_irt_shadow(const texir_scene* s, const float* pos, const float* nrm, c
     if (!s->dev.nodes4) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow: the scene has no 4-wide tree (TEXIR_BVH_WIDTH=2 or the binary fallback): the pass has the 64-texel form only");
     HIP_TRY(launch_irt_shadow(dev_of(s, true), pos, nrm, shift, texel_ids, n, Nt, N, mode, bodies, K, sets, M, out, (unsigned long long*)stats, (float*)workspace,
                               (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
+int64_t texir_irt_shadow_mesh_workspace_bytes(int64_t n_ids, int32_t N, int32_t M)
+{
+    return (int64_t)irt_shadow_mesh_workspace_bytes(n_ids, N, M);
+}
+
+int texir_irt_shadow_mesh(const texir_scene* s, const float* pos, const float* nrm, const float* shift, const int32_t* texel_ids, int64_t n_ids, int64_t Nt,
+                          int32_t N, int32_t mode, const texir_scene* const* occluders, int32_t Q, const int32_t* inst_obj, const float* inst_world_to_obj, int32_t K,
+                          const uint32_t* sets, int32_t M, float* out, uint64_t* stats, uint32_t flags, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    // (the counts first: a caller that sized its buffers by a bad count may hold no buffer at all)
+    if (Q < 0 || Q > 8) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: Q must be in 0..8, got %d (a call takes at most 8 occluders)", Q);
+    if (K < 0 || K > 8) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: K must be in 0..8, got %d (a call takes at most 8 instances; the lost terms of two calls double-count where their objects overlap along a ray)", K);
+    if (M < 1 || M > 8) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: M must be in 1..8, got %d (call again for further sets: the results are independent)", M);
+    if (K > 0 && !inst_obj) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: inst_obj is null");
+    for (int j = 0; j < K; j++)
+        if (inst_obj[j] < 0 || inst_obj[j] >= Q) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: inst_obj[%d] = %d names no occluder (Q = %d)", j, (int)inst_obj[j], Q);
+    if (N < 1 || Nt < 0 || n_ids < 0) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: bad sizes N=%d Nt=%lld n_ids=%lld", N, (long long)Nt, (long long)n_ids);
+    if (mode < 0 || mode > 1) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: mode must be uniform(0) or cosine(1), got %d", mode);
+    if (Nt >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: Nt too large");
+    if (Q > 0 && !occluders) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: occluders is null");
+    for (int q = 0; q < Q; q++)
+        if (!occluders[q]) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: occluders[%d] is null", q);
+    if (K > 0 && !inst_world_to_obj) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: inst_world_to_obj is null");
+    if (!sets) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: sets is null");
+    if (!s || !pos || !nrm || !shift || !out) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: null argument");
+    const int64_t n = texel_ids ? n_ids : Nt;
+    if (n == 0) return TEXIR_OK;
+    const int64_t need = (int64_t)irt_shadow_mesh_workspace_bytes(n, N, M);
+    if (!workspace || workspace_bytes < need)
+        return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: the workspace holds %lld bytes, the call needs %lld (texir_irt_shadow_mesh_workspace_bytes)",
+                    (long long)(workspace ? workspace_bytes : 0), (long long)need);
+    if (!s->dev.nodes4) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: the scene has no 4-wide tree (TEXIR_BVH_WIDTH=2 or the binary fallback): the pass has the 64-texel form only");
+    for (int q = 0; q < Q; q++) {
+        if (!occluders[q]->dev.nodes4) return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: occluders[%d] has no 4-wide tree (TEXIR_BVH_WIDTH=2 or the binary fallback)", q);
+        if (occluders[q]->device != s->device)
+            return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: occluders[%d] lives on device %d, the scene on device %d", q, occluders[q]->device, s->device);
+    }
+    MeshOccluders occ = {};
+    for (int j = 0; j < K; j++) {
+        const texir_scene* o = occluders[inst_obj[j]];
+        occ.nodes4[j] = o->dev.nodes4; occ.nodes4f[j] = o->dev.nodes4f; occ.quads[j] = o->dev.quads;
+        for (int a = 0; a < 6; a++) occ.box[j][a] = o->bounds[a];
+    }
+    HIP_TRY(launch_irt_shadow_mesh(dev_of(s, true), pos, nrm, shift, texel_ids, n, Nt, N, mode, occ, inst_world_to_obj, K, sets, M, !(flags & 1u), out,
+                                   (unsigned long long*)stats, (float*)workspace, (hipStream_t)stream));
     return TEXIR_OK;
 }
 

@@ -96,6 +96,19 @@ size_t irt_shadow_workspace_bytes(int64_t n_ids, int N, int M);      // 0 for ar
 hipError_t launch_irt_shadow(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n_ids, int64_t Nt,
                              int N, int mode, const float* bodies /*dev [K][16]*/, int K, const uint32_t* sets /*dev [M]*/, int M, float* out /*[M][Nt][3]*/,
                              unsigned long long* stats /*nullable*/, float* partial /*>= irt_shadow_workspace_bytes()*/, hipStream_t st);
+// irtshadowmesh.hip: what inserted triangle-mesh objects take from the captured light, per set of instances (the same plan; 4-wide trees).  The geometry of
+// the instances' occluders and their object-space boxes travel BY VALUE in the kernel arguments, per instance (the host resolves instance -> occluder)
+struct MeshOccluders {
+    const float4* nodes4[8];
+    const float4* nodes4f[8];
+    const float4* quads[8];
+    float box[8][6];             // (lo.x, lo.y, lo.z, hi.x, hi.y, hi.z) of the occluder's vertices, object space
+};
+size_t irt_shadow_mesh_workspace_bytes(int64_t n_ids, int N, int M);      // 0 for arguments the launch would refuse
+hipError_t launch_irt_shadow_mesh(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n_ids,
+                                  int64_t Nt, int N, int mode, const MeshOccluders& occ, const float* world_to_obj /*dev [K][12]*/, int K, const uint32_t* sets /*dev [M]*/,
+                                  int M, bool prefilter, float* out /*[M][Nt][3]*/, unsigned long long* stats /*nullable, [3]*/,
+                                  float* partial /*>= irt_shadow_mesh_workspace_bytes()*/, hipStream_t st);
 // irtlight.hip: direct irradiance factors of inserted area lights (quads, spheres) per listed texel, one closest-hit (any = true: any-hit, same bits) query per sample
 hipError_t launch_irt_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n, int64_t Nt,
                              const float* lights /*dev [K][16]*/, int K, int S, float t_max, float* F /*[K][Nt]*/, unsigned long long* stats /*nullable*/, hipStream_t st,

@@ -247,6 +247,12 @@ class TracerO3d(nn.Module):
         # take from the irradiance (Scene.irt_shadow): ir_lights_shadow [K,H,W,3] per lamp and, for K > 1, ir_lights_shadow_all [H,W,3] for all together
         self.irt_light_shadow, self.irt_light_shadow_samples = irt_light_shadow_settings(conf, int(self.sample_l[0]))
         self.ir_lights_shadow = self.ir_lights_shadow_all = None
+        # train.irt_objects / irt_object_samples (optional keys, irtobject.py): none (default) | a list of {obj, pose}: forward() also traces what the inserted
+        # mesh objects take from the irradiance (Scene.irt_shadow_mesh): ir_objects_shadow [K,H,W,3] per object and, for K > 1, ir_objects_shadow_all [H,W,3]
+        from . import irtobject
+        self.irt_objects = irtobject.parse(conf.get(irtobject.KEY, "none"))
+        self.irt_object_samples = irtobject.samples_setting(conf, int(self.sample_l[0]))
+        self.ir_objects_shadow = self.ir_objects_shadow_all = None
         # optional exact texel G-buffer written by the synthetic generator (bypasses the panorama gather)
         self.texel_gbuffer_path = _sibling(self.path_traced_mesh, "texel_gbuffer.npz")
 
@@ -394,6 +400,18 @@ class TracerO3d(nn.Module):
                                       for sets in light_shadow_sets(records.shape[0])]).reshape(-1, H, W, 3)
                     self.ir_lights_shadow = lost[:records.shape[0]]
                     self.ir_lights_shadow_all = lost[records.shape[0]] if lost.shape[0] > records.shape[0] else None
+        if self.irt_objects is not None:
+            if world > 1:
+                raise NotImplementedError("train.irt_objects runs on one GPU (the object pass is not sharded)")
+            with phases.phase("irt_object_shadow"):
+                from . import irtobject
+                occluders, inst, poses = irtobject.load(self.irt_objects, device=self.device)
+                K = len(inst)
+                lost = torch.cat([self.scene.irt_shadow_mesh(pos, nrm, shift, self.irt_object_samples, occluders, inst, poses, sets=sets, mode=self.sample_type[0],
+                                                             texel_ids=ids) for sets in irtobject.shadow_sets(K)]).reshape(-1, H, W, 3)
+                torch.cuda.current_stream().synchronize()       # (the occluder handles are released when this scope ends)
+                self.ir_objects_shadow = lost[:K]
+                self.ir_objects_shadow_all = lost[K] if lost.shape[0] > K else None
         self.ir_texture = irr.reshape(H, W, 3)
         return self.ir_texture
 

@@ -37,6 +37,33 @@ class defer_destroy:
                 _lib._LIB.texir_scene_destroy(_PENDING.pop())
 
 
+def world_to_object(poses):
+    """poses [K,3,4] (or [K,4,4] with the last row 0 0 0 1) OBJECT-TO-WORLD on the host -> [K,12] float32 WORLD-TO-OBJECT rows, the form
+    texir_irt_shadow_mesh reads: inverted in float64, rounded once.  A pose that is not finite, not affine or singular (a condition number of its 3 x 3
+    part above 1e12 counts) raises ValueError naming the instance"""
+    if torch.is_tensor(poses):
+        poses = poses.detach().cpu().numpy()
+    P = np.asarray(poses, np.float64)
+    if P.ndim != 3 or P.shape[1:] not in ((3, 4), (4, 4)):
+        raise ValueError("poses must be [K,3,4] object-to-world (or [K,4,4]), got %r" % (P.shape,))
+    out = np.zeros((P.shape[0], 12), np.float32)
+    for j, p in enumerate(P):
+        if not np.isfinite(p).all():
+            raise ValueError("pose %d has a non-finite entry" % j)
+        if p.shape[0] == 4 and not np.array_equal(p[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("pose %d is not affine: its last row is %r" % (j, p[3].tolist()))
+        A, t = p[:3, :3], p[:3, 3]
+        if np.linalg.det(A) == 0 or not np.linalg.cond(A) < 1e12:
+            raise ValueError("pose %d is singular" % j)
+        Ai = np.linalg.inv(A)
+        w = np.concatenate([Ai, (-Ai @ t)[:, None]], 1)
+        w32 = w.astype(np.float32)
+        if not np.isfinite(w32).all():
+            raise ValueError("pose %d has no float32 inverse" % j)
+        out[j] = w32.reshape(12)
+    return out
+
+
 def _dev_f32(t, device):
     if not torch.is_tensor(t):
         t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))
@@ -335,6 +362,95 @@ class Scene:
             part = None if ids is None else ids[first:first + cnt]
             _lib.check(L.texir_irt_shadow(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(part), cnt, Nt, N, MODES[mode], _lib.ptr(bodies) if K else None,
                                           K, _lib.ptr(masks) if M else None, M, _lib.ptr(out) if M else None, _lib.ptr(st), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()))
+        return (out, st) if stats else out
+
+    # -- the shadow of inserted mesh objects on the captured light (include/texir_hip.h texir_irt_shadow_mesh) --
+    @classmethod
+    def occluder(cls, verts, tris, device=None):
+        """a geometry-only handle for irt_shadow_mesh: verts [V,3], tris [T,3] in OBJECT space (dummy uvs, a 1 x 1 texture)"""
+        tris = np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
+        return cls(verts, tris, np.zeros((3 * tris.shape[0], 2), np.float32), np.zeros((1, 1, 3), np.float32), device=device)
+
+    def bounds(self):
+        """(lo [3], hi [3]) float32: the box of the vertices the triangles name (texir_scene_bounds)"""
+        out = np.zeros(6, np.float32)
+        _lib.check(_lib.lib().texir_scene_bounds(self.h, _lib.ptr(out)))
+        return out[:3].copy(), out[3:].copy()
+
+    def irt_shadow_mesh(self, pos, nrm, shift, n_samples, occluders, instances, poses, sets=None, mode="uniform", texel_ids=None, out=None, stats=False,
+                        prefilter=True, max_workspace_bytes=4 << 30):
+        """what inserted triangle-mesh objects take from the captured irradiance: occluders: Q <= 8 handles of Scene.occluder; instances: K <= 8 indices
+        into them (instance j shows occluder instances[j]; an occluder may stand in the room twice); poses: [K,3,4] OBJECT-TO-WORLD on the host (numpy
+        or a CPU tensor; inverted in float64 and rounded once, a singular pose is a ValueError), or a [K,12] WORLD-TO-OBJECT float32 DEVICE tensor, used in
+        place (a recorded graph replays with whatever it holds then); sets: as irt_shadow's, over the instances (default: one set per instance) -> lost
+        [M, Nt, 3]: lost[m] is the part of irt_generate's irradiance that arrived along rays an instance of set m now intercepts (a union, not a sum), so
+        the irradiance with the objects in the room is max(E - lost[m], 0) (irtlight.add(..., lost=)).  Any point list: texels or a view's pixels.  The
+        id list is walked in slices that are multiples of 64 texels so that the workspace stays under max_workspace_bytes; the cuts do not change a bit.
+        Only listed texels are written.  prefilter=False: every lane queries every instance (the same bits, slower).  stats=True: also int64 [3] =
+        (samples whose ray met some box: the scene rays traced, occluder queries, blocked samples)"""
+        pos = _dev_f32(pos, self.device).reshape(-1, 3)
+        nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
+        Nt = pos.shape[0]
+        shift = _dev_f32(shift, self.device).reshape(Nt, 2)
+        N = int(n_samples)
+        occluders = list(occluders)
+        if not all(isinstance(o, Scene) for o in occluders):
+            raise ValueError("occluders must be Scene handles (Scene.occluder)")
+        inst = np.ascontiguousarray(np.asarray(instances, np.int64).reshape(-1), np.int32)
+        K, Q = int(inst.shape[0]), len(occluders)
+        if torch.is_tensor(poses) and poses.is_cuda:
+            if tuple(poses.shape) != (K, 12) or poses.dtype != torch.float32 or not poses.is_contiguous() or poses.device != self.device:
+                raise ValueError("device poses must be a contiguous float32 [%d,12] world-to-object tensor on %s" % (K, self.device))
+            w2o = poses
+        else:
+            w = world_to_object(poses) if K else np.zeros((0, 12), np.float32)
+            if w.shape[0] != K:
+                raise ValueError("%d instances, %d poses" % (K, w.shape[0]))
+            w2o = torch.from_numpy(w).to(self.device)
+        if sets is None:
+            sets = [[k] for k in range(K)]
+        if torch.is_tensor(sets):
+            masks = sets.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        else:
+            bits = []
+            for m, members in enumerate(sets):
+                v = 0
+                for k in members:
+                    if not 0 <= int(k) < 32:
+                        raise ValueError("set %d names instance %r: indices are 0..31 (bits at or above K are ignored)" % (m, k))
+                    v |= 1 << int(k)
+                bits.append(v - (1 << 32) if v >= 1 << 31 else v)
+            masks = torch.tensor(bits, dtype=torch.int32).reshape(-1).to(self.device)
+        M = int(masks.numel())
+        if out is None:
+            out = torch.zeros((M, Nt, 3), device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (M, Nt, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float32 [%d,%d,3] on %s" % (M, Nt, self.device))
+        st = torch.zeros(3, device=self.device, dtype=torch.int64) if stats else None
+        ids = None
+        n = Nt
+        if texel_ids is not None:
+            ids = texel_ids.to(device=self.device, dtype=torch.int32).contiguous()
+            n = ids.numel()
+        if n == 0:
+            return (out, st) if stats else out
+        L = _lib.lib()
+        handles = (C.c_void_p * max(Q, 1))(*[o.h for o in occluders])
+        per_texel = int(L.texir_irt_shadow_mesh_workspace_bytes(1, N, M))      # (0 for arguments the library refuses: the call below then reports them)
+        step = n
+        if per_texel > 0 and per_texel * n > int(max_workspace_bytes):
+            step = max(64, int(max_workspace_bytes) // per_texel // 64 * 64)
+            if ids is None:
+                ids = torch.arange(Nt, device=self.device, dtype=torch.int32)
+        ws_bytes = max(per_texel * step, 16)
+        ws = torch.empty(ws_bytes, device=self.device, dtype=torch.uint8)
+        for first in range(0, n, step):
+            cnt = min(step, n - first)
+            part = None if ids is None else ids[first:first + cnt]
+            _lib.check(L.texir_irt_shadow_mesh(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(part), cnt, Nt, N, MODES[mode],
+                                               C.cast(handles, C.c_void_p) if Q else None, Q, _lib.ptr(inst) if K else None, _lib.ptr(w2o) if K else None, K,
+                                               _lib.ptr(masks) if M else None, M, _lib.ptr(out) if M else None, _lib.ptr(st), 0 if prefilter else 1, _lib.ptr(ws),
+                                               ws_bytes, _lib.stream_ptr()))
         return (out, st) if stats else out
 
     # -- inserted emitters (include/texir_hip.h texir_irt_lights) ------------------------------------------

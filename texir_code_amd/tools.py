@@ -56,6 +56,13 @@ light as well.  The base is <dir>/0_irr_texture.hdr, or --base <file>, e.g. a 0_
 traced.  --shadow: what the lamps' BODIES take from the base is subtracted first, floored at zero (train.irt_light_shadow: 0_irr_texture_lights_shadow.hdr, the
 union of all bodies, when every light of the directory is named; 0_irr_texture_light<k>_shadow.hdr when one light is named; no other subset has a file).
 Existing files are not overwritten.
+
+    python -m texir_code_amd.tools object-irt <dir> [--object k ...] [--base <file>]
+
+From the files an IrT stage with train.irt_objects wrote into <dir> (0_irr_texture_object<k>_shadow.hdr, what inserted mesh object k takes from the
+irradiance): 0_irr_texture_objects.hdr = max(base - lost, 0).  lost is 0_irr_texture_objects_shadow.hdr, the union of all objects, when every object of the
+directory is named (or none is); 0_irr_texture_object<k>_shadow.hdr when one is named; no other subset has a file.  Nothing is traced.  Existing files are
+not overwritten.
 """
 import sys
 
@@ -260,6 +267,40 @@ def light_irt(directory, lights, base=None, bounce=False, shadow=False):
 
 
 def main(argv):
+    if len(argv) >= 2 and argv[0] == "object-irt":
+        from . import irtobject
+        rest, objects, base, bad = [], [], None, False
+        it = iter(argv[1:])
+        for a in it:
+            key, eq, val = a.partition("=")
+            if key in ("--object", "--base"):
+                val = val if eq else next(it, None)
+                try:
+                    if key == "--object":
+                        objects.append(int(val))
+                    else:
+                        if val is None or base is not None:
+                            raise ValueError
+                        base = val
+                except (TypeError, ValueError):
+                    bad = True
+            elif a.startswith("--"):
+                bad = True
+            else:
+                rest.append(a)
+        if bad or len(rest) != 1 or any(k < 0 for k in objects):
+            print("object-irt needs <dir> [--object k ...] [--base <file>]")
+            return 2
+        try:
+            dst = irtobject.object_irt(rest[0], objects or None, base)
+        except (FileExistsError, FileNotFoundError) as e:
+            print(e)
+            return 1
+        except ValueError as e:
+            print(e)
+            return 2
+        print("wrote", dst)
+        return 0
     if len(argv) >= 2 and argv[0] == "light-irt":
         rest, lights, base, bad, bounce, shadow = [], [], None, False, False, False
         it = iter(argv[1:])

@@ -109,6 +109,14 @@ class IrrTextureRunner:
                         IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_light%d_shadow.hdr" % k), shadow[k].contiguous().cpu().numpy())
                     if shadow_all is not None:
                         IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_lights_shadow.hdr"), shadow_all.contiguous().cpu().numpy())
+            # train.irt_objects (models.TracerO3d): what every inserted mesh object takes from the irradiance, and all of them together
+            shadow, shadow_all = getattr(self.model, "ir_objects_shadow", None), getattr(self.model, "ir_objects_shadow_all", None)
+            if shadow is not None:
+                with phases.phase("write_hdr", sync=False):
+                    for k in range(shadow.shape[0]):
+                        IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_object%d_shadow.hdr" % k), shadow[k].contiguous().cpu().numpy())
+                    if shadow_all is not None:
+                        IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_objects_shadow.hdr"), shadow_all.contiguous().cpu().numpy())
         return irr_texture
 
     def _write_irt(self, irr_texture, path):
