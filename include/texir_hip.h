@@ -358,7 +358,8 @@ TEXIR_API int texir_irt_shadow(const texir_scene* scene, const float* pos /*dev*
  * Caller-owned buffers, the caller's stream, no allocation, no synchronisation, no atomics on results: the call records into a hipGraph.  Q or K outside 0..8,
  * M outside 1..8, inst_obj[j] outside 0..Q-1, N < 1 (all reported before any null buffer), a null buffer, a workspace that is too small, the scene or an
  * occluder without the 4-wide tree and an occluder on another device than the scene are errors with a texir_last_error() text.
- * Not computed here: objects shadowing the inserted emitters' F, R or G; a union with analytic bodies in one call (the two lost terms double-count where they
+ * Not computed here: objects shadowing the inserted emitters' F and R (texir_irt_lights_mesh, texir_spec_lights_mesh do that); the bounce G's own rays,
+ * which still ignore the objects; objects lit by the lamps; a union with analytic bodies in one call (the two lost terms double-count where they
  * overlap); the object's shadow in the specular term; the object drawn in a view; more than 8 occluders, instances or sets per call. */
 TEXIR_API int64_t texir_irt_shadow_mesh_workspace_bytes(int64_t n_ids, int32_t N, int32_t M);
 TEXIR_API int texir_irt_shadow_mesh(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const float* shift /*dev*/,
@@ -933,6 +934,59 @@ TEXIR_API int texir_spec_lights(const texir_scene* scene, const float* pos /*dev
 TEXIR_API int texir_spec_lights_any(const texir_scene* scene, const float* pos /*dev [P,3]*/, const float* nrm /*dev [P,3], raw*/, const float* rough /*dev [P]*/,
                        const float* shift /*dev [P,2]*/, const float* cam /*dev [3]*/, const int32_t* pixel_ids /*dev, nullable = all P*/, int64_t n_ids, int64_t P,
                        const float* lights /*dev [K][16]*/, int32_t K /*0..8*/, int32_t S /*1..65536*/, float t_max, float clamp_eps, float* R /*dev [K][P]*/,
+                       uint64_t* stats /*dev [2], nullable*/, void* stream);
+
+/* ---- inserted emitters BEHIND inserted mesh objects (csrc/irtlightmesh.hip, csrc/speclightmesh.hip): an inserted table darkens the captured light under
+ * it (texir_irt_shadow_mesh); with these two calls it also shadows the inserted lamp above it.
+ *
+ * THE RULE.  texir_irt_lights_mesh is texir_irt_lights, texir_spec_lights_mesh is texir_spec_lights, each with ONE changed step.  SAMPLE, QUAD, SPHERE,
+ * GEOMETRY, the LIGHT SAMPLE and LOBE SAMPLE terms, RESULT (the order of the one float32 accumulator), WRITES, the validation of a record and the FLOAT32
+ * OPERATION SEQUENCES are the text of those rules, word for word.  New inputs, texir_irt_shadow_mesh's with their meaning unchanged:
+ *   occluders   Q in 0..8 geometry-only scene handles (HOST array); their device pointers and boxes enter the kernel arguments by value.
+ *   instances   J in 0..8: instance j = (inst_obj[j] in 0..Q-1, HOST; W[j] = inst_world_to_obj + 12 j, a WORLD-TO-OBJECT 3 x 4 row-major float32 matrix in
+ *               DEVICE memory: a replayed graph sees a moved object, so the host never reads a matrix).  Two instances may name one occluder.
+ *   flags       bit 0 switches the prefilter off.
+ * The changed step:
+ *   VISIBILITY  of the segment (x, d) with bound t_max.  V = 0 iff the scene occludes it, texir_trace_occluded(scene, x, d, 0, t_max) -- which that rule
+ *               proves equal to `the closest hit has t < t_max`, the form texir_irt_lights states -- OR some instance j blocks it:
+ *               texir_trace_occluded(occluder[inst_obj[j]], o', d', 0, t_max), with (o', d') the OBJECT-SPACE RAY of texir_irt_shadow_mesh, its FLOAT32
+ *               OPERATION SEQUENCE unchanged (row by row, nothing normalised: t along (o', d') is t along (x, d), so the bound t_max survives the affine
+ *               map).  A matrix with a non-finite entry never blocks.  An object beyond the light's sample point (every accepted t >= t_max) does not
+ *               block.  Overlapping instances are a union: a segment is blocked once.
+ *   Every question is put as the occlusion query; the entry points have no closest-hit twin.  The bits are those of the closest-hit form by the argument of
+ *   texir_trace_occluded, and the any-hit form is the one profiles/occlusion.json measured faster.
+ * ROUNDING BOUND.  The union of the two rules': the bound e of d of texir_irt_lights (for the lobe sample of texir_spec_lights: the running bound of its d)
+ * is carried into object space by  |dd'_r| <= sum_c |W[r][c]| e_c + 3 u sum_c |W[r][c] d_c|  (o' is exact, as in texir_irt_shadow_mesh), and a triangle's t
+ * along (o', d' +- dd') carries the occlusion query's own bound_t for that direction bound: instance j certainly blocks when a robustly hit triangle has
+ * t + bound_t < t_max, possibly when one has t - bound_t < t_max.  Everything else of the two bounds is unchanged.
+ * PREFILTER.  A lane asks instance j only if (o', d') passes texir_irt_shadow_mesh's box test, the proven one, unchanged: it never fails where the
+ * traversal accepts a triangle, whatever t_max.  (The slab interval is NOT additionally required to meet (0, t_max): that needs its own proof.)
+ * ORDER OF THE QUESTIONS.  One traversal, walked in a wave-uniform loop over {instance 0 .. J-1 whose box some lane's segment meets, scene}: the instances
+ * first.  The answers are functions of the segment alone and V is their OR, so the order changes no bit; it was picked by reasoning, nobody has measured
+ * it: an object's tree is shallow and the room's is deep, and where an object shadows all of a wave's 64 neighbouring points the deep walk is not taken.
+ *   stats dev u64[2], nullable: += samples with g > 0 (terms > 0 for the specular rule), and the visible ones: functions of the inputs alone, whatever order
+ *   the kernel asks its questions in (a blocked segment counts as traced once, however many questions it took).
+ * CONSEQUENCES (the tests hold them).
+ *   - With J = 0, with every matrix non-finite, or where no instance blocks a sample, F, R and stats are bit for bit those of texir_irt_lights /
+ *     texir_spec_lights (and of their _any forms).
+ *   - Where every live sample of a texel is blocked, the result is exactly +0.
+ *   - Float32 addition is monotone and the terms are non-negative: per value F_mesh <= F and R_mesh <= R exactly.
+ *   - List order, duplicates, list cuts, launch shape, stream, graph replay and the prefilter bit change no bit.
+ * Errors: those of texir_irt_lights / texir_spec_lights, and texir_irt_shadow_mesh's conditions on the objects in its text style -- Q or J outside 0..8, an
+ * inst_obj[j] outside 0..Q-1, a null occluder (all reported before any other argument); the scene or an occluder without the 4-wide tree, an occluder on
+ * another device than the scene.  K = 0 and an empty list return 0 and write nothing.  Caller-owned buffers, the caller's stream, no allocation, no
+ * synchronisation, no workspace: the calls record into a hipGraph; records, camera and matrices are read again on every replay.
+ * Not computed: the bounce G's own rays (they still ignore the objects), the objects LIT by the lamps, the object drawn in a view. */
+TEXIR_API int texir_irt_lights_mesh(const texir_scene* scene, const float* pos /*dev [Nt,3]*/, const float* nrm /*dev [Nt,3], raw*/, const float* shift /*dev [Nt,2]*/,
+                       const int32_t* texel_ids /*dev, nullable = all Nt*/, int64_t n_ids, int64_t Nt, const float* lights /*dev [K][16]*/, int32_t K /*0..8*/,
+                       int32_t S /*1..65536*/, float t_max, const texir_scene* const* occluders /*host [Q]*/, int32_t Q /*0..8*/,
+                       const int32_t* inst_obj /*host [J]*/, const float* inst_world_to_obj /*dev [J][12]*/, int32_t J /*0..8*/,
+                       uint32_t flags /*bit 0: prefilter off*/, float* F /*dev [K][Nt]*/, uint64_t* stats /*dev [2], nullable*/, void* stream);
+TEXIR_API int texir_spec_lights_mesh(const texir_scene* scene, const float* pos /*dev [P,3]*/, const float* nrm /*dev [P,3], raw*/, const float* rough /*dev [P]*/,
+                       const float* shift /*dev [P,2]*/, const float* cam /*dev [3]*/, const int32_t* pixel_ids /*dev, nullable = all P*/, int64_t n_ids, int64_t P,
+                       const float* lights /*dev [K][16]*/, int32_t K /*0..8*/, int32_t S /*1..65536*/, float t_max, float clamp_eps,
+                       const texir_scene* const* occluders /*host [Q]*/, int32_t Q /*0..8*/, const int32_t* inst_obj /*host [J]*/,
+                       const float* inst_world_to_obj /*dev [J][12]*/, int32_t J /*0..8*/, uint32_t flags /*bit 0: prefilter off*/, float* R /*dev [K][P]*/,
                        uint64_t* stats /*dev [2], nullable*/, void* stream);
 
 /* ---- host-side codec loops of the file formats around the path (both take HOST pointers) ----------------------------

@@ -27,6 +27,7 @@ def signatures():
     bake = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
     lights = [vp, vp, vp, vp, vp, i64, i64, vp, i32, i32, f32, vp, vp, vp]
     spec_lights = [vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, i32, i32, f32, f32, vp, vp, vp]
+    mesh = [vp, i32, vp, vp, i32, C.c_uint32]      # occluders, Q, inst_obj, inst_world_to_obj, J, flags: before F / R
     return {
         "texir_last_error": (text, []),
         "texir_version": [],
@@ -99,6 +100,8 @@ def signatures():
         "texir_irt_lights_any": lights,
         "texir_spec_lights": spec_lights,
         "texir_spec_lights_any": spec_lights,
+        "texir_irt_lights_mesh": lights[:-3] + mesh + lights[-3:],
+        "texir_spec_lights_mesh": spec_lights[:-3] + mesh + spec_lights[-3:],
         "texir_png_unfilter": [vp, i32, i32, i32, vp],
         "texir_hdr_decode_scanlines": (i64, [vp, i64, i32, i32, vp]),
         "texir_rgbe_encode": [vp, i64, vp],

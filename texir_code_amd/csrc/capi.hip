@@ -577,11 +577,7 @@ int texir_irt_shadow_mesh(const texir_scene* s, const float* pos, const float* n
             return fail(TEXIR_ERR_INVALID, "texir_irt_shadow_mesh: occluders[%d] lives on device %d, the scene on device %d", q, occluders[q]->device, s->device);
     }
     MeshOccluders occ = {};
-    for (int j = 0; j < K; j++) {
-        const texir_scene* o = occluders[inst_obj[j]];
-        occ.nodes4[j] = o->dev.nodes4; occ.nodes4f[j] = o->dev.nodes4f; occ.quads[j] = o->dev.quads;
-        for (int a = 0; a < 6; a++) occ.box[j][a] = o->bounds[a];
-    }
+    for (int j = 0; j < K; j++) mesh_occluder_set(occ, j, occluders[inst_obj[j]]->dev, occluders[inst_obj[j]]->bounds);
     HIP_TRY(launch_irt_shadow_mesh(dev_of(s, true), pos, nrm, shift, texel_ids, n, Nt, N, mode, occ, inst_world_to_obj, K, sets, M, !(flags & 1u), out,
                                    (unsigned long long*)stats, (float*)workspace, (hipStream_t)stream));
     return TEXIR_OK;
@@ -1056,6 +1052,80 @@ int texir_spec_lights_any(const texir_scene* s, const float* pos, const float* n
                           int64_t n_ids, int64_t P, const float* lights, int32_t K, int32_t S, float t_max, float clamp_eps, float* R, uint64_t* stats, void* stream)
 {
     return spec_lights_call("texir_spec_lights_any", true, s, pos, nrm, rough, shift, cam, pixel_ids, n_ids, P, lights, K, S, t_max, clamp_eps, R, stats, stream);
+}
+
+/* ---- inserted emitters behind inserted mesh objects, csrc/irtlightmesh.hip and csrc/speclightmesh.hip (include/texir_hip.h texir_irt_lights_mesh states
+ * the rule).  The conditions on the objects are texir_irt_shadow_mesh's, in its text style, reported before any null buffer; `early`: the counts, `late`:
+ * what needs the handles ---- */
+static int mesh_counts_check(const char* fn, const texir_scene* const* occluders, int32_t Q, const int32_t* inst_obj, int32_t J)
+{
+    if (Q < 0 || Q > 8) return fail(TEXIR_ERR_INVALID, "%s: Q must be in 0..8, got %d (a call takes at most 8 occluders)", fn, Q);
+    if (J < 0 || J > 8) return fail(TEXIR_ERR_INVALID, "%s: J must be in 0..8, got %d (a call takes at most 8 instances)", fn, J);
+    if (J > 0 && !inst_obj) return fail(TEXIR_ERR_INVALID, "%s: inst_obj is null", fn);
+    for (int j = 0; j < J; j++)
+        if (inst_obj[j] < 0 || inst_obj[j] >= Q) return fail(TEXIR_ERR_INVALID, "%s: inst_obj[%d] = %d names no occluder (Q = %d)", fn, j, (int)inst_obj[j], Q);
+    if (Q > 0 && !occluders) return fail(TEXIR_ERR_INVALID, "%s: occluders is null", fn);
+    for (int q = 0; q < Q; q++)
+        if (!occluders[q]) return fail(TEXIR_ERR_INVALID, "%s: occluders[%d] is null", fn, q);
+    return TEXIR_OK;
+}
+
+static int mesh_handles_check(const char* fn, const texir_scene* s, const texir_scene* const* occluders, int32_t Q, const int32_t* inst_obj,
+                              const float* inst_world_to_obj, int32_t J, MeshOccluders& occ)
+{
+    if (J > 0 && !inst_world_to_obj) return fail(TEXIR_ERR_INVALID, "%s: inst_world_to_obj is null", fn);
+    if (!s->dev.nodes4) return fail(TEXIR_ERR_INVALID, "%s: the scene has no 4-wide tree (TEXIR_BVH_WIDTH=2 or the binary fallback): the pass has the 4-wide form only", fn);
+    for (int q = 0; q < Q; q++) {
+        if (!occluders[q]->dev.nodes4) return fail(TEXIR_ERR_INVALID, "%s: occluders[%d] has no 4-wide tree (TEXIR_BVH_WIDTH=2 or the binary fallback)", fn, q);
+        if (occluders[q]->device != s->device)
+            return fail(TEXIR_ERR_INVALID, "%s: occluders[%d] lives on device %d, the scene on device %d", fn, q, occluders[q]->device, s->device);
+    }
+    for (int j = 0; j < J; j++) mesh_occluder_set(occ, j, occluders[inst_obj[j]]->dev, occluders[inst_obj[j]]->bounds);
+    return TEXIR_OK;
+}
+
+int texir_irt_lights_mesh(const texir_scene* s, const float* pos, const float* nrm, const float* shift, const int32_t* texel_ids, int64_t n_ids, int64_t Nt,
+                          const float* lights, int32_t K, int32_t S, float t_max, const texir_scene* const* occluders, int32_t Q, const int32_t* inst_obj,
+                          const float* inst_world_to_obj, int32_t J, uint32_t flags, float* F, uint64_t* stats, void* stream)
+{
+    const char* fn = "texir_irt_lights_mesh";
+    if (int e = mesh_counts_check(fn, occluders, Q, inst_obj, J)) return e;
+    if (K < 0 || K > 8) return fail(TEXIR_ERR_INVALID, "%s: K must be in 0..8, got %d (call again for further lights: the factors add)", fn, K);
+    if (S < 1 || S > 65536) return fail(TEXIR_ERR_INVALID, "%s: S must be in 1..65536, got %d", fn, S);
+    if (!(t_max - t_max == 0.0f)) return fail(TEXIR_ERR_INVALID, "%s: t_max must be finite", fn);
+    if (Nt < 0 || (texel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "%s: negative texel count", fn);
+    if (Nt >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "%s: Nt too large", fn);
+    const int64_t n = texel_ids ? n_ids : Nt;
+    if (K == 0 || n == 0) return TEXIR_OK;
+    if (!s || !pos || !nrm || !shift || !lights || !F) return fail(TEXIR_ERR_INVALID, "%s: null argument (scene, pos, nrm, shift, lights and F are required)", fn);
+    MeshOccluders occ = {};
+    if (int e = mesh_handles_check(fn, s, occluders, Q, inst_obj, inst_world_to_obj, J, occ)) return e;
+    HIP_TRY(launch_irt_lights_mesh(dev_of(s), pos, nrm, shift, texel_ids, n, Nt, lights, K, S, t_max, occ, inst_world_to_obj, J, !(flags & 1u), F,
+                                   (unsigned long long*)stats, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
+int texir_spec_lights_mesh(const texir_scene* s, const float* pos, const float* nrm, const float* rough, const float* shift, const float* cam, const int32_t* pixel_ids,
+                           int64_t n_ids, int64_t P, const float* lights, int32_t K, int32_t S, float t_max, float ceps, const texir_scene* const* occluders, int32_t Q,
+                           const int32_t* inst_obj, const float* inst_world_to_obj, int32_t J, uint32_t flags, float* R, uint64_t* stats, void* stream)
+{
+    const char* fn = "texir_spec_lights_mesh";
+    if (int e = mesh_counts_check(fn, occluders, Q, inst_obj, J)) return e;
+    if (K < 0 || K > 8) return fail(TEXIR_ERR_INVALID, "%s: K must be in 0..8, got %d (call again for further lights: the factors add)", fn, K);
+    if (S < 1 || S > 65536) return fail(TEXIR_ERR_INVALID, "%s: S must be in 1..65536, got %d", fn, S);
+    if (!(t_max - t_max == 0.0f)) return fail(TEXIR_ERR_INVALID, "%s: t_max must be finite", fn);
+    if (!(ceps > 0.0f) || !(ceps - ceps == 0.0f)) return fail(TEXIR_ERR_INVALID, "%s: clamp_eps must be finite and > 0 (got %g)", fn, (double)ceps);
+    if (P < 0 || (pixel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "%s: negative pixel count", fn);
+    if (P >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "%s: P too large", fn);
+    const int64_t n = pixel_ids ? n_ids : P;
+    if (K == 0 || n == 0) return TEXIR_OK;
+    if (!s || !pos || !nrm || !rough || !shift || !cam || !lights || !R)
+        return fail(TEXIR_ERR_INVALID, "%s: null argument (scene, pos, nrm, rough, shift, cam, lights and R are required)", fn);
+    MeshOccluders occ = {};
+    if (int e = mesh_handles_check(fn, s, occluders, Q, inst_obj, inst_world_to_obj, J, occ)) return e;
+    HIP_TRY(launch_spec_lights_mesh(dev_of(s), pos, nrm, rough, shift, cam, pixel_ids, n, P, lights, K, S, t_max, ceps, occ, inst_world_to_obj, J, !(flags & 1u), R,
+                                    (unsigned long long*)stats, (hipStream_t)stream));
+    return TEXIR_OK;
 }
 
 }  // extern "C"

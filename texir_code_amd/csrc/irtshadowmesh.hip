@@ -22,65 +22,14 @@
 
 #include "env.h"
 #include "kernels.h"
+#include "mesh_instance.h"
 
 namespace texir {
-
-constexpr int kMeshMaxInst = 8, kMeshMaxSets = 8;
-constexpr float kBoxPad = 3.814697265625e-06f;        // 2^-18 = 64 u: the pad of a box per unit of (largest |box coordinate| + largest |o'_r|), header
-constexpr float kBoxTiny = 1e-30f;                    // and an absolute term against underflow
-constexpr float kSlabWiden = 4.76837158203125e-07f;   // 2^-21 = 8 u: a slab distance is moved outwards by this share of itself
 
 // waves per SIMD the kernel is compiled for (128 VGPRs): 18 parked words per lane on top of irt_shadow_kernel's state
 template <int MMAX> struct MeshWaves { static constexpr int value = 4; };
 
-// ------------------------------------------------------------------------------------------------
-// the object-space ray and the box test: every product, sum and quotient is its own rounded float32 operation (the header states the arithmetic)
-// ------------------------------------------------------------------------------------------------
-#pragma clang fp contract(off)
-
-__device__ __forceinline__ float row_point(float w0, float w1, float w2, float w3, float x, float y, float z) { return ((w0 * x + w1 * y) + w2 * z) + w3; }
-__device__ __forceinline__ float row_dir(float w0, float w1, float w2, float x, float y, float z) { return (w0 * x + w1 * y) + w2 * z; }
-
-// one slab of the LINE o + t d against [lo, hi] (already padded): narrows (tn, tf); false: the line never enters the slab.  A distance that is not a
-// number (inf - inf after an overflow) narrows nothing: every doubt passes.
-__device__ __forceinline__ bool slab(float lo, float hi, float o, float d, float& tn, float& tf)
-{
-    if (d == 0.f) return o >= lo && o <= hi;
-    const float inv = __builtin_amdgcn_rcpf(d);               // (within 1 ulp; inf for a denormal d: the products below are then +-inf or not a number)
-    const float a = (lo - o) * inv, b = (hi - o) * inv;
-    const float n = a < b ? a : b, f = a < b ? b : a;
-    const float n2 = n - fabsf(n) * kSlabWiden, f2 = f + fabsf(f) * kSlabWiden;
-    tn = n2 > tn ? n2 : tn;
-    tf = f2 < tf ? f2 : tf;
-    return true;
-}
-
-// may the traversal accept a triangle of an object inside the box (lo, hi) for the ray (o, d)?  Never false where it does (header: PREFILTER).
-// rb: the largest |coordinate| of the box
-__device__ __forceinline__ bool box_meets(float lox, float loy, float loz, float hix, float hiy, float hiz, float rb, float ox, float oy, float oz, float dx, float dy,
-                                          float dz)
-{
-    const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
-    const float am = fmaxf(fmaxf(ax, ay), az);
-    if (!(am > 0.f && am < __builtin_inff())) return true;         // a zero or non-finite direction: the question goes to the traversal as it is
-    const float P = kBoxPad * (rb + fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz))) + kBoxTiny;
-    const float lx = lox - P, ly = loy - P, lz = loz - P, hx = hix + P, hy = hiy + P, hz = hiz + P;
-    // the dominant axis as the traversal picks it (device_common.h begin_ray): an accepted triangle has a corner strictly ahead of o along it
-    const int kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
-    const float dk = kz == 0 ? dx : (kz == 1 ? dy : dz), ok = kz == 0 ? ox : (kz == 1 ? oy : oz);
-    const float lk = kz == 0 ? lx : (kz == 1 ? ly : lz), hk = kz == 0 ? hx : (kz == 1 ? hy : hz);
-    if (!(dk > 0.f ? hk > ok : lk < ok)) return false;
-    float tn = -__builtin_inff(), tf = __builtin_inff();
-    if (!slab(lx, hx, ox, dx, tn, tf)) return false;
-    if (!slab(ly, hy, oy, dy, tn, tf)) return false;
-    if (!slab(lz, hz, oz, dz, tn, tf)) return false;
-    return !(tn > tf);
-}
-
-#pragma clang fp contract(fast)
-
-// word `v` of what lane k parked, as a wave-uniform value (k wave-uniform)
-__device__ __forceinline__ float mesh_word(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
+// (the object-space ray row_point / row_dir, the box test box_meets and mesh_word: mesh_instance.h)
 
 template <int MMAX>
 __global__ __launch_bounds__(kBlock, MeshWaves<MMAX>::value) void irt_shadow_mesh_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm,

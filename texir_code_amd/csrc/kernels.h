@@ -104,6 +104,12 @@ struct MeshOccluders {
     const float4* quads[8];
     float box[8][6];             // (lo.x, lo.y, lo.z, hi.x, hi.y, hi.z) of the occluder's vertices, object space
 };
+// instance j of a call shows the occluder with this geometry and this object-space box (the host resolves instance -> occluder)
+inline void mesh_occluder_set(MeshOccluders& occ, int j, const SceneDev& dev, const float bounds[6])
+{
+    occ.nodes4[j] = dev.nodes4; occ.nodes4f[j] = dev.nodes4f; occ.quads[j] = dev.quads;
+    for (int a = 0; a < 6; a++) occ.box[j][a] = bounds[a];
+}
 size_t irt_shadow_mesh_workspace_bytes(int64_t n_ids, int N, int M);      // 0 for arguments the launch would refuse
 hipError_t launch_irt_shadow_mesh(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n_ids,
                                   int64_t Nt, int N, int mode, const MeshOccluders& occ, const float* world_to_obj /*dev [K][12]*/, int K, const uint32_t* sets /*dev [M]*/,
@@ -117,6 +123,15 @@ hipError_t launch_irt_lights(const SceneDev& sc, const float* pos, const float* 
 hipError_t launch_spec_lights(const SceneDev& sc, const float* pos, const float* nrm, const float* rough, const float* shift, const float* cam /*dev [3]*/,
                               const int32_t* ids /*nullable: all P*/, int64_t n, int64_t P, const float* lights /*dev [K][16]*/, int K, int S, float t_max, float ceps,
                               float* R /*[K][P]*/, unsigned long long* stats /*nullable*/, hipStream_t st, bool any = false);
+// irtlightmesh.hip, speclightmesh.hip: the same factors with J inserted mesh instances in the way (every question an occlusion query; 4-wide trees)
+hipError_t launch_irt_lights_mesh(const SceneDev& sc, const float* pos, const float* nrm, const float* shift, const int32_t* ids /*nullable: all Nt*/, int64_t n,
+                                  int64_t Nt, const float* lights /*dev [K][16]*/, int K, int S, float t_max, const MeshOccluders& occ,
+                                  const float* world_to_obj /*dev [J][12]*/, int J, bool prefilter, float* F /*[K][Nt]*/, unsigned long long* stats /*nullable*/,
+                                  hipStream_t st);
+hipError_t launch_spec_lights_mesh(const SceneDev& sc, const float* pos, const float* nrm, const float* rough, const float* shift, const float* cam /*dev [3]*/,
+                                   const int32_t* ids /*nullable: all P*/, int64_t n, int64_t P, const float* lights /*dev [K][16]*/, int K, int S, float t_max,
+                                   float ceps, const MeshOccluders& occ, const float* world_to_obj /*dev [J][12]*/, int J, bool prefilter, float* R /*[K][P]*/,
+                                   unsigned long long* stats /*nullable*/, hipStream_t st);
 // occlusion.hip: is anything in the way inside (t_near, t_far)?  One any-hit query per ray (Open3D RaycastingScene.test_occlusions)
 hipError_t launch_trace_occluded(const SceneDev& sc, const float* org, const float* dir, int64_t R, float t_near, float t_far, uint8_t* occluded,
                                  unsigned long long* stats /*nullable*/, hipStream_t st);

@@ -8,7 +8,9 @@ the IrT stage asks for and the linear algebra of `object-irt`.
 is the identity.  At most 8 objects; two entries may name one file (it is loaded and built once).
 With the key the IrT stage writes, beside 0_irr_texture.hdr, 0_irr_texture_object<k>_shadow.hdr -- the part of the irradiance that arrived along rays object
 k now intercepts -- and for K > 1 0_irr_texture_objects_shadow.hdr, the same for all objects together (a union, not the sum).  `object-irt` subtracts one of
-them from the base: max(E - lost, 0).  Not here: the objects' shadow on inserted emitters' light, the objects drawn in a view."""
+them from the base: max(E - lost, 0).  The objects' shadow on the inserted emitters' light F and R is Scene.irt_lights / spec_lights(occluders=...):
+train.irt_light_objects in the stage, test.objects in the evaluation model.  Not computed: the bounce G's own rays (they ignore the objects), the objects lit
+by the lamps, the objects drawn in a view."""
 import json
 import math
 import os

@@ -127,6 +127,19 @@ def irt_light_shadow_settings(conf, default_samples):
     return on, s
 
 
+def irt_light_objects_setting(conf, lights, objects):
+    """train.irt_light_objects = false (default) | true: the inserted mesh objects (train.irt_objects) also shadow the inserted emitters' light
+    (train.irt_lights): the stage writes 0_irr_texture_light<k>_objects.hdr beside the unchanged 0_irr_texture_light<k>.hdr and, with
+    train.irt_light_bounces >= 1, 0_irr_texture_light<k>_objects_bounce.hdr seeded from the shadowed factor (the bounce's own rays still ignore the
+    objects: not computed).  lights: the value of train.irt_lights; objects: irtobject.parse of train.irt_objects -> bool; ValueError names the keys"""
+    on = conf.get("train.irt_light_objects", False)
+    if not isinstance(on, bool):
+        raise ValueError("train.irt_light_objects must be true or false, got %r" % (on,))
+    if on and (str(lights).lower() == "none" or objects is None):
+        raise ValueError("train.irt_light_objects = true needs train.irt_lights = <json of the lights> and train.irt_objects = <list of {obj, pose}>")
+    return on
+
+
 def light_shadow_sets(K):
     """the sets the stage asks Scene.irt_shadow for, as calls of at most 8 sets: one set per lamp, and for K > 1 the union of all -- one call when
     K + 1 <= 8, else two"""
@@ -253,6 +266,10 @@ class TracerO3d(nn.Module):
         self.irt_objects = irtobject.parse(conf.get(irtobject.KEY, "none"))
         self.irt_object_samples = irtobject.samples_setting(conf, int(self.sample_l[0]))
         self.ir_objects_shadow = self.ir_objects_shadow_all = None
+        # train.irt_light_objects (optional key, irt_light_objects_setting above): false (default) | true: forward() also traces the inserted emitters' factors
+        # with the inserted objects in the way (Scene.irt_lights(occluders=...)): ir_lights_objects [K,H,W], and ir_lights_objects_bounce seeded from it
+        self.irt_light_objects = irt_light_objects_setting(conf, self.irt_lights, self.irt_objects)
+        self.ir_lights_objects = self.ir_lights_objects_bounce = None
         # optional exact texel G-buffer written by the synthetic generator (bypasses the panorama gather)
         self.texel_gbuffer_path = _sibling(self.path_traced_mesh, "texel_gbuffer.npz")
 
@@ -409,6 +426,15 @@ class TracerO3d(nn.Module):
                 K = len(inst)
                 lost = torch.cat([self.scene.irt_shadow_mesh(pos, nrm, shift, self.irt_object_samples, occluders, inst, poses, sets=sets, mode=self.sample_type[0],
                                                              texel_ids=ids) for sets in irtobject.shadow_sets(K)]).reshape(-1, H, W, 3)
+                if self.irt_light_objects:
+                    # the lamps' light with the objects in the way; the bounce is seeded from the shadowed factor, its own rays still ignore the objects
+                    with phases.phase("irt_lights_objects"):
+                        self.ir_lights_objects = self.scene.irt_lights(pos, nrm, shift, torch.from_numpy(records), self.irt_light_samples, texel_ids=ids,
+                                                                        occluders=occluders, instances=inst, poses=poses).reshape(-1, H, W)
+                    if self.irt_light_bounces >= 1:
+                        with phases.phase("irt_light_bounce"):
+                            self.ir_lights_objects_bounce = irtlight.bounce(self.scene, pos, nrm, shift, albedo, self.ir_lights_objects, self.irt_light_bounce_samples,
+                                                                            bounces=self.irt_light_bounces, texel_ids=ids, hw=(H, W), src=src).reshape(-1, H, W, 3)
                 torch.cuda.current_stream().synchronize()       # (the occluder handles are released when this scope ends)
                 self.ir_objects_shadow = lost[:K]
                 self.ir_objects_shadow_all = lost[K] if lost.shape[0] > K else None

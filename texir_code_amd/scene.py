@@ -64,6 +64,28 @@ def world_to_object(poses):
     return out
 
 
+def mesh_instances(device, occluders, instances, poses):
+    """the objects of irt_shadow_mesh, irt_lights and spec_lights in the library's form: occluders: Q <= 8 handles of Scene.occluder; instances: J <= 8
+    indices into them; poses: [J,3,4] OBJECT-TO-WORLD on the host (inverted in float64 and rounded once; a singular pose is a ValueError) or a [J,12]
+    WORLD-TO-OBJECT float32 DEVICE tensor, used in place -> (occluders list, handles array, Q, inst int32 [J], w2o device [J,12], J)"""
+    occluders = list(occluders)
+    if not all(isinstance(o, Scene) for o in occluders):
+        raise ValueError("occluders must be Scene handles (Scene.occluder)")
+    inst = np.ascontiguousarray(np.asarray([] if instances is None else instances, np.int64).reshape(-1), np.int32)
+    K, Q = int(inst.shape[0]), len(occluders)
+    if torch.is_tensor(poses) and poses.is_cuda:
+        if tuple(poses.shape) != (K, 12) or poses.dtype != torch.float32 or not poses.is_contiguous() or poses.device != device:
+            raise ValueError("device poses must be a contiguous float32 [%d,12] world-to-object tensor on %s" % (K, device))
+        w2o = poses
+    else:
+        w = world_to_object(poses) if K else np.zeros((0, 12), np.float32)
+        if w.shape[0] != K:
+            raise ValueError("%d instances, %d poses" % (K, w.shape[0]))
+        w2o = torch.from_numpy(w).to(device)
+    handles = (C.c_void_p * max(Q, 1))(*[o.h for o in occluders])
+    return occluders, handles, Q, inst, w2o, K
+
+
 def _dev_f32(t, device):
     if not torch.is_tensor(t):
         t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))
@@ -393,20 +415,7 @@ class Scene:
         Nt = pos.shape[0]
         shift = _dev_f32(shift, self.device).reshape(Nt, 2)
         N = int(n_samples)
-        occluders = list(occluders)
-        if not all(isinstance(o, Scene) for o in occluders):
-            raise ValueError("occluders must be Scene handles (Scene.occluder)")
-        inst = np.ascontiguousarray(np.asarray(instances, np.int64).reshape(-1), np.int32)
-        K, Q = int(inst.shape[0]), len(occluders)
-        if torch.is_tensor(poses) and poses.is_cuda:
-            if tuple(poses.shape) != (K, 12) or poses.dtype != torch.float32 or not poses.is_contiguous() or poses.device != self.device:
-                raise ValueError("device poses must be a contiguous float32 [%d,12] world-to-object tensor on %s" % (K, self.device))
-            w2o = poses
-        else:
-            w = world_to_object(poses) if K else np.zeros((0, 12), np.float32)
-            if w.shape[0] != K:
-                raise ValueError("%d instances, %d poses" % (K, w.shape[0]))
-            w2o = torch.from_numpy(w).to(self.device)
+        occluders, handles, Q, inst, w2o, K = mesh_instances(self.device, occluders, instances, poses)
         if sets is None:
             sets = [[k] for k in range(K)]
         if torch.is_tensor(sets):
@@ -435,7 +444,6 @@ class Scene:
         if n == 0:
             return (out, st) if stats else out
         L = _lib.lib()
-        handles = (C.c_void_p * max(Q, 1))(*[o.h for o in occluders])
         per_texel = int(L.texir_irt_shadow_mesh_workspace_bytes(1, N, M))      # (0 for arguments the library refuses: the call below then reports them)
         step = n
         if per_texel > 0 and per_texel * n > int(max_workspace_bytes):
@@ -454,14 +462,19 @@ class Scene:
         return (out, st) if stats else out
 
     # -- inserted emitters (include/texir_hip.h texir_irt_lights) ------------------------------------------
-    def irt_lights(self, pos, nrm, shift, lights, n_samples, texel_ids=None, t_max=0.999, out=None, stats=False, query="closest"):
+    def irt_lights(self, pos, nrm, shift, lights, n_samples, texel_ids=None, t_max=0.999, out=None, stats=False, query="closest", occluders=None, instances=None,
+                   poses=None, prefilter=True):
         """direct irradiance factors of inserted area lights: lights [K,16] float32 records (irtlight.pack; a device tensor is used in place, so a
         recorded graph replays with whatever the records hold then), K <= 8 -> F [K, Nt]; the irradiance under emitted radiance c_k is c_k * F[k]
         (irtlight.add).  Any point list: texels or a view's pixels.  t_max: the ray is occluded iff its closest hit has t < t_max in units of the
         segment to the sample point (0.999: a light laid onto a surface is not shadowed by it).  Only listed texels are written.
         stats=True: also int64 [2] = (rays traced, visible ones).  query: 'closest' | 'any' (texir_irt_lights_any: visibility as an occlusion query, the
-        same bits)"""
+        same bits).  occluders, instances, poses, prefilter: inserted mesh objects that shadow the lights, with the meaning, host / device forms and
+        float64 inversion of irt_shadow_mesh (texir_irt_lights_mesh: a segment is also blocked by an instance's triangles inside (0, t_max)).
+        occluders=None calls the entry points above exactly as before; with occluders every question is an occlusion query, so `query` is accepted (and
+        checked) but ignored -- the bits do not depend on it.  prefilter=False: every lane asks every instance (the same bits, slower)"""
         call = "texir_irt_lights_any" if check_query(query) else "texir_irt_lights"
+        mesh = None if occluders is None else mesh_instances(self.device, occluders, instances, poses)
         pos = _dev_f32(pos, self.device).reshape(-1, 3)
         nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
         Nt = pos.shape[0]
@@ -481,7 +494,13 @@ class Scene:
             n_ids = ids.numel()
         st = torch.zeros(2, device=self.device, dtype=torch.int64) if stats else None
         empty = Nt == 0 or (texel_ids is not None and n_ids == 0)          # (an EMPTY id list must not reach the library as "no list = all texels")
-        if not empty:
+        if not empty and mesh is not None:
+            _, handles, Q, inst, w2o, J = mesh
+            _lib.check(_lib.lib().texir_irt_lights_mesh(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(ids), n_ids, Nt,
+                                                        _lib.ptr(lights) if K else None, K, int(n_samples), float(t_max), C.cast(handles, C.c_void_p) if Q else None,
+                                                        Q, _lib.ptr(inst) if J else None, _lib.ptr(w2o) if J else None, J, 0 if prefilter else 1,
+                                                        _lib.ptr(out) if K else None, _lib.ptr(st), _lib.stream_ptr()))
+        elif not empty:
             _lib.check(getattr(_lib.lib(), call)(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(shift), _lib.ptr(ids), n_ids, Nt,
                                                  _lib.ptr(lights) if K else None, K, int(n_samples), float(t_max), _lib.ptr(out) if K else None, _lib.ptr(st),
                                                  _lib.stream_ptr()))
@@ -489,13 +508,17 @@ class Scene:
 
 
     # -- the specular response to inserted emitters (include/texir_hip.h texir_spec_lights) -----------------
-    def spec_lights(self, pos, nrm, rough, shift, cam, lights, n_samples, texel_ids=None, t_max=0.999, clamp_eps=1e-14, query="closest", out=None, stats=False):
+    def spec_lights(self, pos, nrm, rough, shift, cam, lights, n_samples, texel_ids=None, t_max=0.999, clamp_eps=1e-14, query="closest", out=None, stats=False,
+                    occluders=None, instances=None, poses=None, prefilter=True):
         """specular (GGX) response factors of inserted area lights per pixel: pos, nrm [P,3] (pos already offset), rough [P], shift [P,2] (the pixels'
         specular shift), cam [3], lights [K,16] float32 records (irtlight.pack; a device tensor is used in place, as is a device cam, so a recorded graph
         replays with whatever they hold then), K <= 8 -> R [K, P]; the radiance a light of colour c_k adds to the view is c_k * R[k] beside its diffuse
         albedo / pi * c_k * F[k] (irtlight.add_view).  Balance-heuristic multiple importance sampling over the light's area and the GGX lobe, n_samples
-        points each.  t_max, query, stats, out, texel_ids (here: pixel ids): as irt_lights.  clamp_eps: the material model's floor of denominators."""
+        points each.  t_max, query, stats, out, texel_ids (here: pixel ids): as irt_lights.  clamp_eps: the material model's floor of denominators.
+        occluders, instances, poses, prefilter: inserted mesh objects that shadow the lights, as irt_lights takes them (texir_spec_lights_mesh); with
+        occluders `query` is accepted but ignored."""
         call = "texir_spec_lights_any" if check_query(query) else "texir_spec_lights"
+        mesh = None if occluders is None else mesh_instances(self.device, occluders, instances, poses)
         pos = _dev_f32(pos, self.device).reshape(-1, 3)
         nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
         P = pos.shape[0]
@@ -517,7 +540,14 @@ class Scene:
             n_ids = ids.numel()
         st = torch.zeros(2, device=self.device, dtype=torch.int64) if stats else None
         empty = P == 0 or (texel_ids is not None and n_ids == 0)           # (an EMPTY id list must not reach the library as "no list = all pixels")
-        if not empty:
+        if not empty and mesh is not None:
+            _, handles, Q, inst, w2o, J = mesh
+            _lib.check(_lib.lib().texir_spec_lights_mesh(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(rough), _lib.ptr(shift), _lib.ptr(cam), _lib.ptr(ids), n_ids,
+                                                         P, _lib.ptr(lights) if K else None, K, int(n_samples), float(t_max), float(clamp_eps),
+                                                         C.cast(handles, C.c_void_p) if Q else None, Q, _lib.ptr(inst) if J else None,
+                                                         _lib.ptr(w2o) if J else None, J, 0 if prefilter else 1, _lib.ptr(out) if K else None, _lib.ptr(st),
+                                                         _lib.stream_ptr()))
+        elif not empty:
             _lib.check(getattr(_lib.lib(), call)(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(rough), _lib.ptr(shift), _lib.ptr(cam), _lib.ptr(ids), n_ids, P,
                                                  _lib.ptr(lights) if K else None, K, int(n_samples), float(t_max), float(clamp_eps),
                                                  _lib.ptr(out) if K else None, _lib.ptr(st), _lib.stream_ptr()))

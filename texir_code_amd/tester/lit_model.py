@@ -6,6 +6,7 @@
     test.light_bounce_samples = 256   samples per texel and bounce
     test.light_shadows = false        the shadow the lamps' bodies cast on the captured diffuse light (Scene.irt_shadow), traced once at construction
     test.light_shadow_samples = 256   samples per texel
+    test.objects = none               | <irtobject list or json, the form of train.irt_objects>: inserted mesh objects that shadow the lamps' light
 
 With lights, render() adds their diffuse and specular response to every rendered view, sum_k colour_k (albedo / pi F[k] + R[k]) (Scene.irt_lights,
 Scene.spec_lights, irtlight.add_view), at test.light_samples samples per pixel, light and technique, with the pixels' own specular shift and the model's
@@ -15,12 +16,15 @@ it with the very call that fetches the irradiance texture, and render() adds alb
 fixed seed: the CPU generator's stream stays what it is.  With test.light_shadows the model builds, once and on the same texel G-buffer with the same
 private generator, `lost`: what the union of the lamps' bodies takes from the captured irradiance; forward() fetches it like the irradiance texture and
 render() takes albedo / pi * (irr - max(irr - lost, 0)) from the diffuse term before the lamps' light is added (irtlight.add_view(lost=, irr=)).
+With test.objects (it needs test.lights) the objects are loaded once (irtobject.load) and handed to the irt_lights and spec_lights calls of render()
+and to the F that seeds the bounce: the lamps' diffuse and specular light is shadowed by the objects (Scene.irt_lights(occluders=...)).  Not computed with
+objects: the bounce's own rays (they still ignore the objects), the objects lit by the lamps, the objects drawn in the view, their shadow on captured light.
 Not computed: the bodies' shadow in the specular term of captured light, bodies shadowing each other's light, the body drawn in the view, a specular bounce.
 With the default `none` the class IS its base: every file Editing, View, Relighting and Error write is unchanged byte for byte.
 This is the class the plugin registry hands the tester runners for models.test_nvdiffrast.MaterialModel."""
 import torch
 
-from .. import gbuffer as GB, irtlight, texpost
+from .. import gbuffer as GB, irtlight, irtobject, texpost
 from ..texture import texture as tex_fetch
 from . import test_model as TM
 
@@ -33,6 +37,21 @@ def load_test_lights(spec, device):
         return None
     records, colours = irtlight.load(spec)
     return torch.from_numpy(records).to(device), torch.from_numpy(colours).to(device)
+
+
+def load_test_objects(spec, lights, device):
+    """test.objects: none -> None; an irtobject list or json (the form of train.irt_objects) -> the keywords Scene.irt_lights / spec_lights take:
+    {occluders, instances, poses}, loaded once.  It needs test.lights: a ValueError names both keys"""
+    try:
+        objects = irtobject.parse(spec)
+    except (ValueError, FileNotFoundError) as e:
+        raise type(e)(str(e).replace(irtobject.KEY, "test.objects"))
+    if objects is None:
+        return None
+    if lights is None:
+        raise ValueError("test.objects needs test.lights = <json of the lights>: the objects shadow the inserted emitters' light")
+    occluders, inst, poses = irtobject.load(objects, device=device)
+    return {"occluders": occluders, "instances": inst, "poses": poses}
 
 
 def light_bounce_settings(conf):
@@ -68,6 +87,7 @@ class MaterialModel(TM.MaterialModel):
         super().__init__(conf, *args, **kwargs)
         self.test_lights = load_test_lights(str(conf.get("test.lights", "none")), self.device)
         self.light_samples = int(conf.get("test.light_samples", 64))
+        self.test_objects = load_test_objects(conf.get("test.objects", "none"), self.test_lights, self.device)
         self.light_bounces, self.light_bounce_samples = light_bounce_settings(conf)
         self.bounce_tex = None
         self.light_shadows, self.light_shadow_samples = light_shadow_settings(conf)
@@ -100,7 +120,7 @@ class MaterialModel(TM.MaterialModel):
         """sum_k colour_k G[k] on the irradiance texture's grid, file orientation -> self.bounce_tex [H,W,3] (device)"""
         records, colours = self.test_lights
         H, W, pos, nrm, shift, ids, covered = self._texel_inputs()
-        F = self.scene.irt_lights(pos, nrm, shift, records, int(self.light_samples), texel_ids=ids).reshape(-1, H, W)
+        F = self.scene.irt_lights(pos, nrm, shift, records, int(self.light_samples), texel_ids=ids, **(getattr(self, "test_objects", None) or {})).reshape(-1, H, W)
         src = None
         if (H, W) == tuple(self.scene.tex_shape[:2]):
             src = texpost.pad_texture(covered.reshape(H, W, 1).to(torch.float32), return_src=True)[1]
@@ -141,8 +161,9 @@ class MaterialModel(TM.MaterialModel):
         records, colours = lights
         n_l = int(getattr(self, "light_samples", 64))
         pts, nrm, alb = points.reshape(P, 3), normal.reshape(P, 3), albedo.reshape(P, 3)
-        F = self.scene.irt_lights(pts, nrm, shift_s, records, n_l)
-        R = self.scene.spec_lights(pts, nrm, roughness.reshape(P), shift_s, cam_position, records, n_l, clamp_eps=TM.TINY_NUMBER)
+        objects = getattr(self, "test_objects", None) or {}                  # (none: the calls are the ones they were)
+        F = self.scene.irt_lights(pts, nrm, shift_s, records, n_l, **objects)
+        R = self.scene.spec_lights(pts, nrm, roughness.reshape(P), shift_s, cam_position, records, n_l, clamp_eps=TM.TINY_NUMBER, **objects)
         G, lost = getattr(self, "_bounce_irr", None), getattr(self, "_shadow_irr", None)
         if lost is None:
             res["rgb"] = irtlight.add_view(res["rgb"].reshape(P, 3), alb, F, R, colours, G=None if G is None else G.reshape(P, 3)).reshape(shape + (3,))

@@ -47,7 +47,7 @@ From the files an IrT stage with train.irt_split wrote into <dir> (0_irr_texture
 class off).  --replace: class k's texels become ONE colour instead, colour * 0_irr_texture_unit<k>.hdr (train.irt_split_unit; the reference's "lamp texels
 become one colour", models/test_nvdiffrast.py:109-110).  Irradiance is linear in the radiance texture: nothing is traced.  Existing files are not overwritten.
 
-    python -m texir_code_amd.tools light-irt <dir> --light k --colour r,g,b [--light j --colour r,g,b ...] [--base <file>] [--bounce] [--shadow]
+    python -m texir_code_amd.tools light-irt <dir> --light k --colour r,g,b [--light j --colour r,g,b ...] [--base <file>] [--bounce] [--shadow] [--objects]
 
 From the files an IrT stage with train.irt_lights wrote into <dir> (0_irr_texture_light<k>.hdr, the irradiance under inserted emitter k at unit radiance):
 0_irr_texture_lit.hdr = base + sum colour_k * 0_irr_texture_light<k>.hdr -- the listed emitters switched on at those radiances.  Direct light only,
@@ -55,7 +55,9 @@ unless --bounce: then colour_k * 0_irr_texture_light<k>_bounce.hdr (train.irt_li
 light as well.  The base is <dir>/0_irr_texture.hdr, or --base <file>, e.g. a 0_irr_texture_relit.hdr from relight-irt.  Irradiance is linear in emitted radiance: nothing is
 traced.  --shadow: what the lamps' BODIES take from the base is subtracted first, floored at zero (train.irt_light_shadow: 0_irr_texture_lights_shadow.hdr, the
 union of all bodies, when every light of the directory is named; 0_irr_texture_light<k>_shadow.hdr when one light is named; no other subset has a file).
-Existing files are not overwritten.
+--objects: the files with the inserted mesh objects in the way of the lamps' light take the plain ones' place (train.irt_light_objects:
+0_irr_texture_light<k>_objects.hdr, and 0_irr_texture_light<k>_objects_bounce.hdr with --bounce); together with object-irt this gives the full relit atlas:
+light-irt <dir> ... --objects --base <dir>/0_irr_texture_objects.hdr.  Existing files are not overwritten.
 
     python -m texir_code_amd.tools object-irt <dir> [--object k ...] [--base <file>]
 
@@ -209,8 +211,9 @@ def relight_irt(directory, k, colour, replace=False):
     return dst
 
 
-def light_irt(directory, lights, base=None, bounce=False, shadow=False):
-    """lights: [(k, (r, g, b)), ...]; bounce: also the lights' bounce files; shadow: the bodies' shadow on the base first -> the path written.
+def light_irt(directory, lights, base=None, bounce=False, shadow=False, objects=False):
+    """lights: [(k, (r, g, b)), ...]; bounce: also the lights' bounce files; shadow: the bodies' shadow on the base first; objects: the files with the
+    inserted mesh objects in the way (train.irt_light_objects) in place of the plain ones -> the path written.
     FileExistsError / FileNotFoundError / ValueError name what is wrong"""
     import os
     from . import irtlight
@@ -225,8 +228,11 @@ def light_irt(directory, lights, base=None, bounce=False, shadow=False):
     E = np.asarray(IO.read_hdr(base), np.float32)
     F = []
     for k, _ in lights:
-        f = os.path.join(directory, "0_irr_texture_light%d.hdr" % k)
+        f = os.path.join(directory, "0_irr_texture_light%d%s.hdr" % (k, "_objects" if objects else ""))
         if k < 0 or not os.path.exists(f):
+            if objects:
+                raise FileNotFoundError("--light %d --objects needs %s: run the IrT stage with train.irt_light_objects = true (and train.irt_lights, "
+                                        "train.irt_objects)" % (k, f))
             raise FileNotFoundError("--light %d needs %s: run the IrT stage with train.irt_lights = <json of the lights>" % (k, f))
         img = np.asarray(IO.read_hdr(f), np.float32)
         if img.shape != E.shape:
@@ -254,8 +260,11 @@ def light_irt(directory, lights, base=None, bounce=False, shadow=False):
     if bounce:
         G = []
         for k, _ in lights:
-            f = os.path.join(directory, "0_irr_texture_light%d_bounce.hdr" % k)
+            f = os.path.join(directory, "0_irr_texture_light%d%s_bounce.hdr" % (k, "_objects" if objects else ""))
             if not os.path.exists(f):
+                if objects:
+                    raise FileNotFoundError("--bounce --objects needs %s: run the IrT stage with train.irt_light_objects = true and train.irt_light_bounces >= 1 "
+                                            "(and train.irt_light_albedo)" % f)
                 raise FileNotFoundError("--bounce needs %s: run the IrT stage with train.irt_light_bounces >= 1 (and train.irt_light_albedo)" % f)
             img = np.asarray(IO.read_hdr(f), np.float32)
             if img.shape != E.shape:
@@ -302,7 +311,7 @@ def main(argv):
         print("wrote", dst)
         return 0
     if len(argv) >= 2 and argv[0] == "light-irt":
-        rest, lights, base, bad, bounce, shadow = [], [], None, False, False, False
+        rest, lights, base, bad, bounce, shadow, objects = [], [], None, False, False, False, False
         it = iter(argv[1:])
         for a in it:
             key, eq, val = a.partition("=")
@@ -326,15 +335,17 @@ def main(argv):
                 bounce = True
             elif a == "--shadow":
                 shadow = True
+            elif a == "--objects":
+                objects = True
             elif a.startswith("--"):
                 bad = True
             else:
                 rest.append(a)
         if bad or len(rest) != 1 or not lights or any(c is None for _, c in lights):
-            print("light-irt needs <dir> --light k --colour r,g,b [--light k --colour r,g,b ...] [--base <file>] [--bounce] [--shadow]")
+            print("light-irt needs <dir> --light k --colour r,g,b [--light k --colour r,g,b ...] [--base <file>] [--bounce] [--shadow] [--objects]")
             return 2
         try:
-            dst = light_irt(rest[0], [(k, c) for k, c in lights], base, bounce, shadow)
+            dst = light_irt(rest[0], [(k, c) for k, c in lights], base, bounce, shadow, objects)
         except (FileExistsError, FileNotFoundError) as e:
             print(e)
             return 1

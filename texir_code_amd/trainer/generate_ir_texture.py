@@ -101,6 +101,16 @@ class IrrTextureRunner:
                 with phases.phase("write_hdr", sync=False):
                     for k in range(bounce.shape[0]):
                         IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_light%d_bounce.hdr" % k), bounce[k].contiguous().cpu().numpy())
+            # train.irt_light_objects (models.TracerO3d): the same two kinds of file with the inserted objects in the way of the lamps' light
+            lights_obj, bounce_obj = getattr(self.model, "ir_lights_objects", None), getattr(self.model, "ir_lights_objects_bounce", None)
+            if lights_obj is not None:
+                with phases.phase("write_hdr", sync=False):
+                    for k in range(lights_obj.shape[0]):
+                        IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_light%d_objects.hdr" % k),
+                                     lights_obj[k][..., None].expand(-1, -1, 3).contiguous().cpu().numpy())
+                    if bounce_obj is not None:
+                        for k in range(bounce_obj.shape[0]):
+                            IO.write_hdr(target.replace("0_irr_texture.hdr", "0_irr_texture_light%d_objects_bounce.hdr" % k), bounce_obj[k].contiguous().cpu().numpy())
             # train.irt_light_shadow (models.TracerO3d): what every inserted emitter's body takes from the irradiance, and all of them together
             shadow, shadow_all = getattr(self.model, "ir_lights_shadow", None), getattr(self.model, "ir_lights_shadow_all", None)
             if shadow is not None:
