@@ -442,7 +442,15 @@ TEXIR_API int texir_scene_set_corner_normals(texir_scene* scene, const float* co
  * Outputs, P = 6*c*c, all dev: pos [P,3] (interpolated vertex position; empty -> (1,0,0)), nrm [P,3] (interpolated
  * corner normals; empty -> (1,0,0)), mask [P] (1 where rast[...,3] > 0), uv [P,2] (= texc), uv_da [P,4]
  * (= texd: du/dX, du/dY, dv/dX, dv/dY per pixel), tri_id [P] (primitive id + 1, 0 = empty; nvdiffrast rast[...,3]).
- * flip_v: 1 -> uv.v := 1 - v (pyredner's OBJ convention for the nvdiffrast-side textures). */
+ * flip_v: 1 -> uv.v := 1 - v (pyredner's OBJ convention for the nvdiffrast-side textures), and the two dv entries of uv_da negated.
+ *   RAYS start at the eye (the pre-image of clip (0,0,1,0)) and are not clipped: no near or far plane, the closest hit with t > 0 counts.  mvp and
+ *     s * mvp (s != 0, either sign) are the same projective map and give the same G-buffer.
+ *   NORMALS are not renormalised: with corner normals w n0 + u n1 + v n2 as given; without, the unit geometric normal cross(v1 - v0, v2 - v0) /
+ *     |cross| in the CALLER's winding (the library's stored corner order is a rotation of the caller's and keeps the sign).
+ *   BACKGROUND values ignore flip_v: pos = nrm = (1,0,0), uv = (0,0), uv_da = 0, mask = 0, tri_id = 0.
+ *   ERRORS: TEXIR_ERR_INVALID, with nothing launched and no output written, for cube_res outside 1..16384, for a singular mvp and for an affine one
+ *     (an orthographic camera: the inverse's row 2 has w == 0, there is no eye).
+ * Every pixel is compared with a float64 reference built from mvp, c and the mesh alone (tests/gbuffer_cases.py, tests/test_gpu_gbuffer_cast.py). */
 TEXIR_API int texir_gbuffer_cast(const texir_scene* scene, const float* mvp /*host*/, int32_t cube_res, int32_t flip_v,
                        float* pos, float* nrm, float* mask, float* uv, float* uv_da, int32_t* tri_id, void* stream);
 

@@ -687,6 +687,7 @@ int texir_gbuffer_cast(const texir_scene* s, const float* mvp, int32_t c, int32_
 {
     if (!s || !mvp || !pos || !nrm || !mask || !uv || !uv_da || !tri_id) return fail(TEXIR_ERR_INVALID, "texir_gbuffer_cast: null argument");
     if (c <= 0 || c > 16384) return fail(TEXIR_ERR_INVALID, "texir_gbuffer_cast: bad cube_res %d", c);
+    if (!gbuffer_mvp_ok(mvp)) return fail(TEXIR_ERR_INVALID, "texir_gbuffer_cast: an mvp is singular or affine (no eye)");
     HIP_TRY(launch_gbuffer(dev_of(s), mvp, (const float4*)s->d_cnrm, c, flip_v, pos, nrm, mask, uv, uv_da, tri_id, (hipStream_t)stream));
     return TEXIR_OK;
 }

@@ -107,29 +107,42 @@ static bool invert4(const double* m, double* out)
 // (0,0,1,0)), and for a pixel at ndc (x,y) the world point at ANY depth z is X_h = x r0 + y r1 + z r2 + r3, so
 //   dir(x,y) = X_h.xyz - eye * X_h.w = x A0 + y A1 + A3,   Ak = rk.xyz - eye * rk.w     (the z term cancels exactly).
 // Evaluated in double on the host: in float32 X_h.w suffers catastrophic cancellation for n = 1e-4, f = 100.
+// One face's basis from its mvp; false where the camera has none: a singular mvp, or an affine one (r2.w == 0: no eye, e.g. an orthographic projection).
+static bool face_basis(const float* mvp16, FaceBasis& fb)
+{
+    double m[16], mi[16];
+    for (int k = 0; k < 16; k++) m[k] = (double)mvp16[k];
+    if (!invert4(m, mi)) return false;
+    const double* r0 = mi, *r1 = mi + 4, *r2 = mi + 8, *r3 = mi + 12;
+    if (r2[3] == 0.0) return false;                              // not a perspective camera
+    double eye[3] = {r2[0] / r2[3], r2[1] / r2[3], r2[2] / r2[3]};
+    double wfar = r2[3] + r3[3];                                 // X_h.w of the face centre on the far plane
+    double sgn = wfar < 0.0 ? -1.0 : 1.0;
+    for (int k = 0; k < 3; k++) {
+        fb.eye[k] = (float)eye[k];
+        fb.dx[k] = (float)(sgn * (r0[k] - eye[k] * r0[3]));
+        fb.dy[k] = (float)(sgn * (r1[k] - eye[k] * r1[3]));
+        fb.d0[k] = (float)(sgn * (r3[k] - eye[k] * r3[3]));
+    }
+    // normalise the scale of the basis (direction length is irrelevant; keeps t in sane float range)
+    double len = sqrt((double)fb.d0[0] * fb.d0[0] + (double)fb.d0[1] * fb.d0[1] + (double)fb.d0[2] * fb.d0[2]);
+    if (len > 0.0) for (int k = 0; k < 3; k++) { fb.d0[k] = (float)(fb.d0[k] / len); fb.dx[k] = (float)(fb.dx[k] / len); fb.dy[k] = (float)(fb.dy[k] / len); }
+    return true;
+}
+
+// the caller's argument check: every face of mvp [6,4,4] HOST has a basis
+bool gbuffer_mvp_ok(const float* mvp_host)
+{
+    FaceBasis fb;
+    for (int f = 0; f < 6; f++) if (!face_basis(mvp_host + 16 * f, fb)) return false;
+    return true;
+}
+
 hipError_t launch_gbuffer(const SceneDev& sc, const float* mvp_host, const float4* cnrm, int c, int flip_v, float* pos, float* nrm, float* mask,
                           float* uv, float* uvda, int32_t* tri, hipStream_t st)
 {
     GbufArgs g;
-    for (int f = 0; f < 6; f++) {
-        double m[16], mi[16];
-        for (int k = 0; k < 16; k++) m[k] = (double)mvp_host[16 * f + k];
-        if (!invert4(m, mi)) return hipErrorInvalidValue;
-        const double* r0 = mi, *r1 = mi + 4, *r2 = mi + 8, *r3 = mi + 12;
-        if (r2[3] == 0.0) return hipErrorInvalidValue;               // not a perspective camera
-        double eye[3] = {r2[0] / r2[3], r2[1] / r2[3], r2[2] / r2[3]};
-        double wfar = r2[3] + r3[3];                                 // X_h.w of the face centre on the far plane
-        double sgn = wfar < 0.0 ? -1.0 : 1.0;
-        for (int k = 0; k < 3; k++) {
-            g.face[f].eye[k] = (float)eye[k];
-            g.face[f].dx[k] = (float)(sgn * (r0[k] - eye[k] * r0[3]));
-            g.face[f].dy[k] = (float)(sgn * (r1[k] - eye[k] * r1[3]));
-            g.face[f].d0[k] = (float)(sgn * (r3[k] - eye[k] * r3[3]));
-        }
-        // normalise the scale of the basis (direction length is irrelevant; keeps t in sane float range)
-        double len = sqrt((double)g.face[f].d0[0] * g.face[f].d0[0] + (double)g.face[f].d0[1] * g.face[f].d0[1] + (double)g.face[f].d0[2] * g.face[f].d0[2]);
-        if (len > 0.0) for (int k = 0; k < 3; k++) { g.face[f].d0[k] = (float)(g.face[f].d0[k] / len); g.face[f].dx[k] = (float)(g.face[f].dx[k] / len); g.face[f].dy[k] = (float)(g.face[f].dy[k] / len); }
-    }
+    for (int f = 0; f < 6; f++) if (!face_basis(mvp_host + 16 * f, g.face[f])) return hipErrorInvalidValue;
     g.cnrm = cnrm; g.c = c; g.flip_v = flip_v; g.pos = pos; g.nrm = nrm; g.mask = mask; g.uv = uv; g.uvda = uvda; g.tri = tri;
     const dim3 grid(grid_capped(kBlock, (int64_t)6 * c * c));
     if (sc.nodes4) hipLaunchKernelGGL(gbuffer_kernel<4>, grid, dim3(kBlock), 0, st, sc, g);

@@ -38,6 +38,7 @@ size_t loss_workspace_bytes(int64_t P, int C, int R);
 hipError_t launch_loss(int stage, int l2, const float* gt, const float* rgb, const float* albedo, const float* rough, const float* rough_womip,
                        const float* empty, const float* gtm, const uint8_t* seg, const uint8_t* hl, const uint8_t* room, int64_t P, int C, int R,
                        int hw, void* workspace, float* out, float* d_rgb, float* d_albedo, float* d_rough, hipStream_t st);
+bool gbuffer_mvp_ok(const float* mvp_host);      // every face of mvp [6,4,4] has an eye: not singular, not affine
 hipError_t launch_gbuffer(const SceneDev& sc, const float* mvp_host, const float4* cnrm, int c, int flip_v, float* pos, float* nrm, float* mask,
                           float* uv, float* uvda, int32_t* tri, hipStream_t st);
 int mip_levels(int H, int W, int max_mip_level);
