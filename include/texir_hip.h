@@ -374,6 +374,14 @@ TEXIR_API int texir_irt_shadow_mesh(const texir_scene* scene, const float* pos /
  * decision, so that bench.py's roofline names the kernel that really ran.  buf receives a NUL-terminated string. */
 TEXIR_API int texir_irt_kernel_name(const texir_scene* scene, int64_t n_ids, int32_t N, char* buf, int32_t cap);
 
+/* The INSTANTIATION of that form the same call launches for sampling mode `mode` (uniform 0 | cosine 1) and estimator `cosine_estimator` (0: the IrT
+ * estimator of texir_irt_generate; 1: the cosine branch of texir_diffuse_irradiance, which needs mode 1).  The 64-texel form has instantiations compiled
+ * for what the IrrT stage calls it with -- N a power of two, 4-byte texels in 8x4-texel lines (texture layout 4), a scene with the float node copy:
+ * "irt_group_kernel<false, 4, 6, IrtFixed<mode, estimator>>"; they compute the bits of the generic kernel.  Every other call, and every call under
+ * TEXIR_IRT_SPECIALISE=0, gets the name texir_irt_kernel_name reports.  Like that name this is the PLAIN launch's kernel: a counting launch (texir_irt_generate
+ * with `stats`) of the 64-texel form always runs the generic kernel's counting instantiation, irt_group_kernel<true, 4, 6>. */
+TEXIR_API int texir_irt_kernel_variant(const texir_scene* scene, int64_t n_ids, int32_t N, int32_t mode, int32_t cosine_estimator, char* buf, int32_t cap);
+
 /* Replaces MaterialModel.render + specular_reflectance (models/mat_nvdiffrast.py:201-249, 260-279), forward:
  *   rgb = irr*albedo/pi + (1/S) sum_i Ls_i * w_i(roughness)        
  * normal,albedo,points,irr [P,3] dev; rough [P] dev; cam [3] dev; shift [P,2] dev (GGX sample shift, as above)

@@ -58,6 +58,7 @@ def signatures():
         "texir_irt_shadow_mesh_workspace_bytes": (i64, [i64, i32, i32]),
         "texir_irt_shadow_mesh": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, C.c_uint32, vp, i64, vp],
         "texir_irt_kernel_name": [vp, i64, i32, text, i32],
+        "texir_irt_kernel_variant": [vp, i64, i32, i32, i32, text, i32],
         "texir_spec_forward": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp],
         "texir_spec_forward_train": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp, vp],
         "texir_spec_backward_ws": [vp, vp, vp, vp, i64, i32, vp, vp, vp],

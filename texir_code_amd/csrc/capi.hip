@@ -607,6 +607,16 @@ int texir_irt_kernel_name(const texir_scene* s, int64_t n_ids, int32_t N, char* 
     return TEXIR_OK;
 }
 
+int texir_irt_kernel_variant(const texir_scene* s, int64_t n_ids, int32_t N, int32_t mode, int32_t cosine_estimator, char* buf, int32_t cap)
+{
+    if (!s || !buf || cap < 1) return fail(TEXIR_ERR_INVALID, "texir_irt_kernel_variant: null argument");
+    if (mode < 0 || mode > 1 || cosine_estimator < 0 || cosine_estimator > 1 || (cosine_estimator && mode != 1))
+        return fail(TEXIR_ERR_INVALID, "texir_irt_kernel_variant: mode must be uniform(0) or cosine(1), the cosine estimator goes with mode 1; got %d, %d", mode, cosine_estimator);
+    const IrtPlan p = irt_plan(s->dev, n_ids, N, mode | (cosine_estimator ? 4 : 0));
+    snprintf(buf, (size_t)cap, "%s", p.variant);
+    return TEXIR_OK;
+}
+
 // texir_spec_forward and its training form, which also keeps d w_i / d roughness (dw_ws) and so always needs the Ls_ws workspace
 static int spec_forward_call(const char* fn, bool train, const texir_scene* s, const float* normal, const float* albedo, const float* rough, const float* points,
                              const float* irr, const float* cam, const float* shift, int64_t P, int32_t S, float clamp_eps, int32_t ls_given, float* rgb, float* Ls_ws,

@@ -28,6 +28,9 @@ struct SceneDev {
     int sched_weight;      // phase scheduler of trace_closest: weight of the lanes at inner nodes (2; 1 for scenes whose node steps run less than ~60 % full: texir_scene_tune measures it once per scene)
 };
 
+// the hit shader's view of a scene (shade_hit): irt_group_kernel's fixed form fills it from its kernel arguments at the hit
+struct ShadeDev { const float4* uvs; const float* tex; int Ht, Wt, tiles_x; };
+
 constexpr int kBlock = 256;          // 4 waves
 constexpr int kLdsStack = 24;        // default: entries per lane kept in LDS (24 KiB per block)
 constexpr int kSentinel = 0x7FFFFFFF;
@@ -53,8 +56,11 @@ constexpr int kLstk = kLdsStack / 2;                    // the single-ray tracin
 
 // sample_util.py:41  float32(double(i)/double(N)).  For N = 2^k (and i < 2^24) the quotient is exact in float32, so the
 // multiply by the exact reciprocal gives the identical value without a float64 division.
+// POW2: the caller guarantees N = 2^k <= 2^24 (i < N), so only the exact-reciprocal arm is compiled (the same expression: the same bits)
+template <bool POW2 = false>
 __device__ __forceinline__ float ham0(uint32_t i, uint32_t N)
 {
+    if constexpr (POW2) return (float)i * (1.0f / (float)N);
     if ((N & (N - 1u)) == 0u && i < (1u << 24)) return (float)i * (1.0f / (float)N);
     return (float)((double)i / (double)N);
 }
@@ -88,9 +94,14 @@ __device__ __forceinline__ Frame make_frame(float nx, float ny, float nz)
     return f;
 }
 
-// cos/sin of the polar angle for the three modes (:115-143)
+// cos/sin of the polar angle for the three modes (:115-143).  MODE >= 0: the mode is the caller's compile-time constant (`mode` is not read) and only
+// its arm is compiled -- the arm's expressions are the run-time form's
+template <int MODE = -1>
 __device__ __forceinline__ void polar(int mode, float s0, float rough, float& ct, float& st)
 {
+    if constexpr (MODE == 0) { ct = 1.0f - s0; st = sqrtf(1.0f - ct * ct); return; }
+    else if constexpr (MODE == 1) { ct = sqrtf(1.0f - s0); st = sqrtf(1.0f - ct * ct); return; }
+    else if constexpr (MODE >= 2) mode = MODE;
     if (mode == 0) { ct = 1.0f - s0; st = sqrtf(1.0f - ct * ct); }
     else if (mode == 1) { ct = sqrtf(1.0f - s0); st = sqrtf(1.0f - ct * ct); }
     else {
@@ -102,10 +113,11 @@ __device__ __forceinline__ void polar(int mode, float s0, float rough, float& ct
 }
 
 // (sin / cos of phi from libm's sincosf, ~70 instructions: the form that is pinned at 5e-6 on the reference's own directions)
+template <int MODE = -1>
 __device__ __forceinline__ void sample_dir(int mode, float s0, float s1, float rough, const Frame& f, float* L)
 {
     float ct, st;
-    polar(mode, s0, rough, ct, st);
+    polar<MODE>(mode, s0, rough, ct, st);
     float sp, cp;
     float phi = 6.283185307179586f * s1 - 3.141592653589793f;
     sincosf(phi, &sp, &cp);
@@ -125,15 +137,19 @@ __device__ __forceinline__ Texel load_texel(const float* __restrict__ pos, const
 }
 
 // direction of sample i of N of a texel with shifts (sh0, sh1) and frame f, as the IrT kernels take it (no roughness: modes 0, 1)
+// (MODE, POW2: the compile-time arms of polar and ham0)
+template <int MODE = -1, bool POW2 = false>
 __device__ __forceinline__ void texel_sample_dir(int mode, uint32_t i, uint32_t N, float sh0, float sh1, const Frame& f, float* d)
 {
-    const float s0 = shift_wrap_clamp(ham0(i, N), sh0);
+    const float s0 = shift_wrap_clamp(ham0<POW2>(i, N), sh0);
     const float s1 = shift_wrap_clamp(ham1(i), sh1);
-    sample_dir(mode, s0, s1, 0.f, f, d);
+    sample_dir<MODE>(mode, s0, s1, 0.f, f, d);
 }
 
 // corner uvs of the triangle in leaf slot `slot`: a = (uv0, uv1), b = (uv2, -, -)
-__device__ __forceinline__ void tri_uvs(const SceneDev& sc, int slot, float4& a, float4& b)
+// (SC: SceneDev, or any view of it that has `uvs`)
+template <typename SC>
+__device__ __forceinline__ void tri_uvs(const SC& sc, int slot, float4& a, float4& b)
 {
     // one 32-byte record per quad record: (q0, q1), (q2, q3); the even slot is triangle (q0, q1, q2), the odd one (q3, q2, q1)  (bvh_build.h)
     const size_t rec = (size_t)(slot >> 1);
@@ -192,7 +208,10 @@ __device__ __forceinline__ void unpack_texel(uint32_t q, float& r, float& g, flo
 // ------------------------------------------------------------------------------------------------
 // hit shader: query_irf post-intersection math (tracer_o3d_irt.py:248-267)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void shade_hit(const SceneDev& sc, int tri_slot, float bu, float bv, float* rgb)
+// LAYOUT >= 0: the texture layout is the caller's compile-time constant (sc.tex_layout is not read) and only its arm is compiled.  SC: SceneDev, or a view
+// of it that has uvs, tex, Ht, Wt, tiles_x (ShadeDev: what irt_group_kernel's fixed form re-reads from its kernel arguments per hit)
+template <int LAYOUT = -1, typename SC = SceneDev>
+__device__ __forceinline__ void shade_hit(const SC& sc, int tri_slot, float bu, float bv, float* rgb)
 {
     float u = fminf(fmaxf(bu, 0.f), 1.f), v = fminf(fmaxf(bv, 0.f), 1.f);      // :250 np.clip
     float4 a, b;
@@ -216,11 +235,13 @@ __device__ __forceinline__ void shade_hit(const SceneDev& sc, int tri_slot, floa
     // Where the four taps live.  The values read are the same in every layout (the retiled copies hold the identical floats), so
     // the result is bit-identical; what changes is how many 128-byte lines a fetch touches: row-major 2 rows 12*Wt bytes apart
     // (2.4 lines on average), layout 2 exactly one line (any 2x2 footprint lies inside the 3x3 tile of (x0/2, y0/2)).
-    if (sc.tex_layout >= 3) {
+    int layout;
+    if constexpr (LAYOUT >= 0) layout = LAYOUT; else layout = sc.tex_layout;
+    if (layout >= 3) {
         // one 128-byte line of 4-byte texels holds the whole footprint: two adjacent-dword loads
         const uint32_t* t;
         int pitch;
-        if (sc.tex_layout == 3) {
+        if (layout == 3) {
             t = (const uint32_t*)sc.tex + ((size_t)(y0 >> 2) * sc.tiles_x + (x0 >> 2)) * 32 + ((y0 & 3) * 5 + (x0 & 3));
             pitch = 5;
         } else {
@@ -242,10 +263,10 @@ __device__ __forceinline__ void shade_hit(const SceneDev& sc, int tri_slot, floa
         return;
     }
     const float *p00, *p10, *p01, *p11;
-    if (sc.tex_layout == 2) {
+    if (layout == 2) {
         const float* t = sc.tex + ((size_t)(y0 >> 1) * sc.tiles_x + (x0 >> 1)) * 32 + ((y0 & 1) * 3 + (x0 & 1)) * 3;
         p00 = t; p10 = t + 3; p01 = t + 9; p11 = t + 12;
-    } else if (sc.tex_layout == 1) {
+    } else if (layout == 1) {
         auto at = [&](int x, int y) { return sc.tex + (((size_t)(y >> 3) * sc.tiles_x + (x >> 3)) * 64 + ((y & 7) * 8 + (x & 7))) * 3; };
         p00 = at(x0, y0); p10 = at(x1, y0); p01 = at(x0, y1); p11 = at(x1, y1);
     } else {
@@ -342,7 +363,8 @@ constexpr int kWiCulled = 2 + kProbeSlots, kWiOverflow = 3 + kProbeSlots, kWiSlo
 // its stack at the end of that leaf: the pop that ends the leaf finds nothing and the lane is finished, nothing is drained.  The accept test is the one
 // expression of the closest-hit form: a triangle's t and its inside test do not depend on h.t.
 struct NoNext { };
-template <bool STATS, int LSTK, int WIDTH, bool STREAM, bool ANY, typename Next>
+// HAVE_F: the caller guarantees sc.nodes4f (the float node copy) is present, so `agree` does not test the pointer
+template <bool STATS, int LSTK, int WIDTH, bool STREAM, bool ANY, typename Next, bool HAVE_F = false>
 __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy, float oz, float dx, float dy, float dz,
                                           uint32_t& n_nodes, uint32_t& n_tris, uint32_t* wave_iters, int refill_at, Next&& next, float t_start, float t_near)
 {
@@ -384,12 +406,12 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
             const unsigned long long m = __ballot(has);
             const int src = m ? __ffsll((long long)m) - 1 : 0;
             son = (uint32_t)__builtin_amdgcn_readlane((int)lon, src);
-            signs_uniform = WIDTH == 4 && sc.nodes4f != nullptr && !__any(has && lon != son);
+            signs_uniform = WIDTH == 4 && (HAVE_F || sc.nodes4f != nullptr) && !__any(has && lon != son);
             kz0 = __builtin_amdgcn_readlane(kz, src);
             kz_uniform = !__any(has && kz != kz0);
         } else {
             son = (uint32_t)__builtin_amdgcn_readfirstlane((int)lon);
-            signs_uniform = WIDTH == 4 && sc.nodes4f != nullptr && !__any(lon != son);
+            signs_uniform = WIDTH == 4 && (HAVE_F || sc.nodes4f != nullptr) && !__any(lon != son);
             kz0 = __builtin_amdgcn_readfirstlane(kz);
             kz_uniform = !__any(kz != kz0);
         }
@@ -758,11 +780,11 @@ __device__ __forceinline__ Hit trace_core(const SceneDev& sc, float ox, float oy
 // closest hit of one ray per lane, run to completion (all lanes of the wave enter and leave together).  One instance per kernel: it
 // owns the LDS part of the stacks.  STATS: n_nodes / n_tris count this lane's node fetches and triangle tests; wave_iters[0/1] (if
 // given) count, on the first active lane, how many times the wave executed the node-step and the triangle-test bodies.
-template <bool STATS, int LSTK = kLdsStack, int WIDTH = 2>
+template <bool STATS, int LSTK = kLdsStack, int WIDTH = 2, bool HAVE_F = false>
 __device__ __forceinline__ Hit trace_closest(const SceneDev& sc, float ox, float oy, float oz, float dx, float dy, float dz,
                                              uint32_t& n_nodes, uint32_t& n_tris, uint32_t* wave_iters = nullptr)
 {
-    return trace_core<STATS, LSTK, WIDTH, false, false>(sc, ox, oy, oz, dx, dy, dz, n_nodes, n_tris, wave_iters, 64, NoNext{}, __builtin_inff(), 0.f);
+    return trace_core<STATS, LSTK, WIDTH, false, false, NoNext, HAVE_F>(sc, ox, oy, oz, dx, dy, dz, n_nodes, n_tris, wave_iters, 64, NoNext{}, __builtin_inff(), 0.f);
 }
 
 // Streamed form: every ray of the lane, the first one included, comes from `next`, which is called for the idle lanes once `refill_at` of them have

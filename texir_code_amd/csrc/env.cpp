@@ -30,6 +30,7 @@ static Env parse()
     v.box_slack_log2 = geti("TEXIR_BOX_SLACK_LOG2", -19);
     const int pw = geti("TEXIR_IRT_TEXELS_PER_WAVE", 0);
     v.irt_texels_per_wave = (pw == 1 || pw == 64) ? pw : 0;
+    v.irt_specialise = geti("TEXIR_IRT_SPECIALISE", 1) != 0;
     const int rf = geti("TEXIR_IRT_REFILL", 0);
     v.irt_refill = (rf >= 1 && rf <= 63) ? rf : 0;
     const int mc = geti("TEXIR_IRT_MIN_PART_CELLS", 8);
@@ -57,6 +58,7 @@ int env_switch(const char* name, int* value)
         {"TEXIR_TEX_LAYOUT", g_env.tex_layout}, {"TEXIR_SCHED_WEIGHT", g_env.sched_weight}, {"TEXIR_MIP_PER_LEVEL", g_env.mip_per_level},
         {"TEXIR_ADAM_SCALAR", g_env.adam_scalar}, {"TEXIR_ADAM_GRID_Y", g_env.adam_grid_y}, {"TEXIR_MAX_LEAF", g_env.max_leaf},
         {"TEXIR_BOX_SLACK_LOG2", g_env.box_slack_log2}, {"TEXIR_IRT_TEXELS_PER_WAVE", g_env.irt_texels_per_wave}, {"TEXIR_IRT_REFILL", g_env.irt_refill},
+        {"TEXIR_IRT_SPECIALISE", g_env.irt_specialise},
         {"TEXIR_IRT_MIN_PART_CELLS", g_env.irt_min_part_cells}, {"TEXIR_IRT_LOG2PARTS", g_env.irt_log2parts_cap},
         {"TEXIR_IRT_GRID_CAP", g_env.irt_grid_cap}, {"TEXIR_SPEC_GRID_CAP", g_env.spec_grid_cap}, {"TEXIR_SPEC_LPP", g_env.spec_lpp},
         {"TEXIR_ATROUS_LDS_PASSES", g_env.atrous_lds_passes}};

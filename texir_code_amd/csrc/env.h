@@ -16,6 +16,7 @@ struct Env {
     int max_leaf;              // TEXIR_MAX_LEAF             0 = builder default | 1..8 triangles per leaf (quad leaves, the default build: capped at 4)
     int box_slack_log2;        // TEXIR_BOX_SLACK_LOG2       -19 (default) | 99 = no slack
     int irt_texels_per_wave;   // TEXIR_IRT_TEXELS_PER_WAVE  0 = automatic | 1 | 64
+    int irt_specialise;        // TEXIR_IRT_SPECIALISE       1 (default): the 64-texel form runs its fixed instantiation where the call matches it (kernels.hip IrtFixed) | 0 = always the generic one (same bits)
     int irt_refill;            // TEXIR_IRT_REFILL           0 = lock-step passes (default) | 1..63: refill idle lanes once this many have gathered (irt_stream_kernel)
     int irt_min_part_cells;    // TEXIR_IRT_MIN_PART_CELLS   8 (default)
     int irt_log2parts_cap;     // TEXIR_IRT_LOG2PARTS        -1 = no cap

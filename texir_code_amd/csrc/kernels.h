@@ -16,8 +16,10 @@ hipError_t irt_probe_node_utilisation(const SceneDev& sc, const float* pos, cons
                                       int N, int mode, unsigned long long* work, hipStream_t st, double* util);
 // out[q][t] of K planes of Nt texels = irt_scale of the listed texels' part sums partial[part][q][k][3], added in part order (K = 1: Nt is not used)
 hipError_t launch_irt_combine(const float* partial, const int32_t* ids /*nullable*/, int64_t n_ids, int64_t Nt, int K, int parts, int N, float two, float* out, hipStream_t st);
-struct IrtPlan { int per_wave, log2parts, width; char name[64]; };
-IrtPlan irt_plan(const SceneDev& sc, int64_t n_ids, int N);      // the kernel form launch_irt picks for this call
+// `name`: the kernel FORM (what every mode of a call shape shares); `fixed` / `variant`: whether launch_irt runs the form's fixed instantiation for this
+// `mode` (sampling mode, kEstimatorCosine or-ed in), and the instantiation's full name
+struct IrtPlan { int per_wave, log2parts, width; bool fixed; char name[64]; char variant[96]; };
+IrtPlan irt_plan(const SceneDev& sc, int64_t n_ids, int N, int mode = 0);      // the kernel launch_irt picks for this call
 hipError_t launch_prefetch(const void* p, size_t bytes, int blocks, uint32_t* sink, hipStream_t st);
 size_t tex_retile_bytes(int Ht, int Wt, int layout, int* tiles_x, int* tiles_y);
 hipError_t launch_tex_retile(const float* src_row_major, float* dst, int Ht, int Wt, int layout, hipStream_t st);

@@ -103,8 +103,18 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_kernel(SceneDev sc, c
     if (STATS) irt_stats_flush(stats, lane, c_rays, c_nodes, c_tris, c_hits, wi);
 }
 
+// What irt_group_kernel knows at compile time.  IrtAny: nothing -- any N, any mode, either estimator, any texture layout, with or without the float node copy.
+// IrtFixed<MODE, COSW>: the call the IrrT stage and the bench make -- N = 2^k <= 2^24 (log2N >= 0), sampling mode MODE, estimator COSW, 4-byte texels in
+// 8x4-texel lines (layout 4), float nodes present.  Each fixed arm evaluates the expressions of the generic one in the same order (same bits); what goes is
+// the wave-uniform selects around them and the scalar registers they hold across the traversal loop.  launch_irt picks the form (irt_plan).
+// Measured on c4 (profiles/r10): the fixed arms alone 1407.3 ms against the generic kernel's 1406.3 -- nothing; with the shader's scene fields read at the
+// hit (below) 1374.3.  Per-region instruction and v_readlane counts of both kernels: tools/isa_regions.py.
+struct IrtAny { static constexpr bool fixed = false; static constexpr int mode = -1; static constexpr bool cosw = false; static constexpr int layout = -1; };
+template <int MODE, bool COSW>
+struct IrtFixed { static constexpr bool fixed = true; static constexpr int mode = MODE; static constexpr bool cosw = COSW; static constexpr int layout = 4; };
+
 // Multi-texel passes: GRP neighbouring texels per wave, all taking the same absolute direction cell in a pass (device_common.h sample_index_m, cell_to_pass_m).
-template <bool STATS, int WIDTH, int LOG2GRP>
+template <bool STATS, int WIDTH, int LOG2GRP, typename FIX = IrtAny>
 __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm,
                                                            const float* __restrict__ shift, const int32_t* __restrict__ ids, int64_t n_ids,
                                                            int N, int log2N, int mode, float* __restrict__ irr,
@@ -116,13 +126,13 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
     const int grp = lane >> LOG2M, sub = lane & (M - 1);
     const int n_cells = N >> LOG2M;
     uint32_t cn = 0, ct = 0, c_rays = 0, c_hits = 0, wi[kWiSlots] = {0};
-    const bool cosw = (mode & kEstimatorCosine) != 0;
+    const bool cosw = FIX::fixed ? FIX::cosw : (mode & kEstimatorCosine) != 0;
     mode &= 3;
     // A chunk = GRP texels x (all passes / 2^log2parts).  With parts > 1 the raw partial sums go to partial[part][k][3] and
     // irt_combine_kernel adds them in part order: the result depends on N only, never on how the texel list is cut or scheduled.
     const int part_cells = n_cells >> log2parts;
     // Which cells a part holds: an azimuthal wedge of the hemisphere (device_common.h wedge_cell); the hand-out below keeps neighbouring wedges on one XCD.
-    const int cell_bits = log2N < 0 ? 0 : log2N - LOG2M, bphi = (cell_bits + 1) >> 1, bth = cell_bits - bphi;
+    const int cell_bits = (!FIX::fixed && log2N < 0) ? 0 : log2N - LOG2M, bphi = (cell_bits + 1) >> 1, bth = cell_bits - bphi;
     // XCD-aware hand-out: the 8 XCDs have private 4 MiB L2s; with ONE chunk counter consecutive chunks -- the 32 parts of the
     // same 64 texels -- go to whichever waves ask next, so every L2 sees every direction of every region.  Here each XCD owns parts / 8
     // neighbouring wedges (a 45-degree sector at N = 2048) of ALL texel groups and pulls them from its own counter (its own 128-byte line: 8
@@ -159,7 +169,7 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
         const Frame f = make_frame(nx, ny, nz);
         float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
         for (int Lc = part * part_cells; Lc < (part + 1) * part_cells; Lc++) {
-            const int J = log2N >= 0 ? wedge_cell(Lc, bphi, bth) : Lc;
+            const int J = (FIX::fixed || log2N >= 0) ? wedge_cell(Lc, bphi, bth) : Lc;
 #if TEXIR_CHAIN_PROBE
             const bool pass_timed = (Lc & 7) == 0;
             uint32_t pass_c0 = 0;
@@ -168,22 +178,31 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
 #endif
             if (live) {
                 // (N not a power of two: only the one-sample-per-pass form is launched, in natural sample order)
-                const uint32_t i = log2N < 0 ? (uint32_t)J : sample_index_m(cell_to_pass_m((uint32_t)J, sh0, sh1, log2N, LOG2M), (uint32_t)sub, log2N, LOG2M);
+                const uint32_t i = (!FIX::fixed && log2N < 0) ? (uint32_t)J : sample_index_m(cell_to_pass_m((uint32_t)J, sh0, sh1, log2N, LOG2M), (uint32_t)sub, log2N, LOG2M);
                 float d[3];
-                texel_sample_dir(mode, i, (uint32_t)N, sh0, sh1, f, d);
+                texel_sample_dir<FIX::mode, FIX::fixed>(mode, i, (uint32_t)N, sh0, sh1, f, d);
                 const float ndl = cosw ? 1.f : fminf(fmaxf(nx * d[0] + ny * d[1] + nz * d[2], 0.f), 1.f);       // :170, RAW normal (before the trace: one live register instead of three)
 #if TEXIR_CHAIN_PROBE
                 uint32_t tr_c0 = 0, tr_c1 = 0;
                 if (pass_timed) tr_c0 = probe_clock();
-                Hit h = trace_closest<STATS, kGroupLstk, WIDTH>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, wi);
+                Hit h = trace_closest<STATS, kGroupLstk, WIDTH, FIX::fixed>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, wi);
                 if (pass_timed) { tr_c1 = probe_clock(); probe_add(pv[13], tr_c1 - tr_c0); probe_add(pv[12], 1u); }
 #else
-                Hit h = trace_closest<STATS, kGroupLstk, WIDTH>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, STATS ? wi : nullptr);
+                Hit h = trace_closest<STATS, kGroupLstk, WIDTH, FIX::fixed>(sc, px, py, pz, d[0], d[1], d[2], cn, ct, STATS ? wi : nullptr);
 #endif
                 if (STATS) c_rays++;
                 if (h.slot >= 0 && h.t > 1e-4f) {          // tracer_o3d_irt.py:248
                     float L[3];
-                    shade_hit(sc, h.slot, h.u, h.v, L);
+                    if constexpr (FIX::fixed) {
+                        // What only the shader needs of the scene (uv and texture base, Ht, Wt, tiles_x) is read here, from the kernel's argument block
+                        // through the scalar cache, instead of being held across the traversal loop -- where it does not fit into the scalar file and is parked
+                        // in VGPR lanes, read back one v_readlane per dword and pass.  `sc` is the first argument: offset 0 of the block.  The empty asm
+                        // makes the address a value of this point of the program, so the loads stay behind the traversal.
+                        const SceneDev __attribute__((address_space(4)))* ka = (const SceneDev __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+                        asm volatile("" : "+s"(ka));
+                        const ShadeDev sd = {ka->uvs, ka->tex, ka->Ht, ka->Wt, ka->tiles_x};
+                        shade_hit<FIX::layout>(sd, h.slot, h.u, h.v, L);
+                    } else shade_hit<FIX::layout>(sc, h.slot, h.u, h.v, L);
                     acc0 += L[0] * ndl; acc1 += L[1] * ndl; acc2 += L[2] * ndl;
                     if (STATS) c_hits++;
                 }
@@ -618,7 +637,9 @@ static int irt_forced_texels_per_wave() { return env().irt_texels_per_wave; }
 // 64 texels per wave: the passes of a texel are cut into 2^log2parts ranges of >= 64 passes (N = 2048: 32 ranges), each range its
 // own chunk.  Fine chunks matter for lists up to ~1 M texels (262 k texels: 8 ranges 14.1, 32 ranges 15.7 Grays/s), i.e. for every
 // rank's share of a multi-GPU run; the number of ranges depends on N alone, so results do not depend on the sharding.
-IrtPlan irt_plan(const SceneDev& sc, int64_t n_ids, int N)
+// The fixed instantiation of the 64-texel form (IrtFixed) runs where the call is what it was compiled for: N = 2^k <= 2^24, 4-byte texels in 8x4 lines, float
+// nodes present, and one of the three (sampling mode, estimator) pairs the C-ABI's entry points produce.  TEXIR_IRT_SPECIALISE=0: never (A/B runs, parity tests).
+IrtPlan irt_plan(const SceneDev& sc, int64_t n_ids, int N, int mode)
 {
     IrtPlan p{};
     const int forced = irt_forced_texels_per_wave();
@@ -630,6 +651,12 @@ IrtPlan irt_plan(const SceneDev& sc, int64_t n_ids, int N)
     const bool stream = p.per_wave == 64 && env().irt_refill && pow2 && p.log2parts > 0;
     if (stream) snprintf(p.name, sizeof(p.name), "irt_stream_kernel<false, %d>", p.width);
     else snprintf(p.name, sizeof(p.name), p.per_wave == 64 ? "irt_group_kernel<false, %d, 6>" : "irt_kernel<false, %d>", p.width);
+    const bool cosw = (mode & kEstimatorCosine) != 0;
+    const int smode = mode & 3;
+    p.fixed = env().irt_specialise && p.per_wave == 64 && !stream && pow2 && N <= (1 << 24) && sc.tex_layout == 4 && sc.nodes4f != nullptr &&
+              ((smode == 0 && !cosw) || smode == 1);
+    if (p.fixed) snprintf(p.variant, sizeof(p.variant), "irt_group_kernel<false, 4, 6, IrtFixed<%d, %s>>", smode, cosw ? "true" : "false");
+    else snprintf(p.variant, sizeof(p.variant), "%s", p.name);
     return p;
 }
 
@@ -662,7 +689,7 @@ hipError_t launch_irt(const SceneDev& sc, const float* pos, const float* nrm, co
     if (e != hipSuccess) return e;
     const bool pow2 = (N & (N - 1)) == 0;
     const int l2 = ilog2_exact(N);
-    const IrtPlan plan = irt_plan(sc, n_ids, N);
+    const IrtPlan plan = irt_plan(sc, n_ids, N, mode);
 #if TEXIR_CHAIN_PROBE
     const bool probe_group = stats && sc.nodes4 && plan.per_wave == 64 && !(env().irt_refill && pow2 && plan.log2parts > 0);
 #else
@@ -697,6 +724,10 @@ hipError_t launch_irt(const SceneDev& sc, const float* pos, const float* nrm, co
     else if (per_wave == 1) go(irt_kernel<true, 4>, irt_kernel<false, 4>, n_ids, l2);
     // compaction by refill (A/B switch TEXIR_IRT_REFILL = lanes that must be idle before a refill)
     else if (env().irt_refill && pow2 && log2parts > 0) go(irt_stream_kernel<true, 4>, irt_stream_kernel<false, 4>, chunks, l2, env().irt_refill);
+    // the fixed instantiations (irt_plan); the counting form stays generic
+    else if (plan.fixed && (mode & 3) == 0) go(irt_group_kernel<true, 4, 6>, irt_group_kernel<false, 4, 6, IrtFixed<0, false>>, chunks, l2);
+    else if (plan.fixed && !(mode & kEstimatorCosine)) go(irt_group_kernel<true, 4, 6>, irt_group_kernel<false, 4, 6, IrtFixed<1, false>>, chunks, l2);
+    else if (plan.fixed) go(irt_group_kernel<true, 4, 6>, irt_group_kernel<false, 4, 6, IrtFixed<1, true>>, chunks, l2);
     else go(irt_group_kernel<true, 4, 6>, irt_group_kernel<false, 4, 6>, chunks, pow2 ? l2 : -1);  // any N (natural sample order if not 2^k)
     if (log2parts) {
         const hipError_t launched = launch_irt_combine(partial, ids, n_ids, 0 /*one class: no plane stride*/, 1, 1 << log2parts, N, (mode & kEstimatorCosine) ? 1.f : 2.f, irr, st);

@@ -156,6 +156,12 @@ class Scene:
         _lib.check(_lib.lib().texir_irt_kernel_name(self.h, int(n_ids), int(n_samples), buf, 96))
         return buf.value.decode()
 
+    def irt_kernel_variant(self, n_ids, n_samples, mode="uniform", cosine_estimator=False):
+        """the instantiation of that form the call launches for this sampling mode and estimator (include/texir_hip.h texir_irt_kernel_variant)"""
+        buf = C.create_string_buffer(128)
+        _lib.check(_lib.lib().texir_irt_kernel_variant(self.h, int(n_ids), int(n_samples), MODES[mode], int(bool(cosine_estimator)), buf, 128))
+        return buf.value.decode()
+
     def set_texture(self, tex):
         """tex [Ht,Wt,3] tensor (device or host) -- stage -1's temporary light-source-only texture (mat_nvdiffrast.py:141-150)"""
         if torch.is_tensor(tex) and tex.is_cuda:

@@ -60,7 +60,8 @@ def child(workload, spp, probe):
         sc.irt_generate(d_pos, d_nrm, d_shift, spp, "uniform", texel_ids=ids, out=irr)
     b.record()
     torch.cuda.synchronize()
-    out = {"kernel_ms": a.elapsed_time(b), "rays": int(ids.numel()) * spp, "n_ids": int(ids.numel()), "spp": spp, "kernel": sc.irt_kernel_name(int(ids.numel()), spp)}
+    out = {"kernel_ms": a.elapsed_time(b), "rays": int(ids.numel()) * spp, "n_ids": int(ids.numel()), "spp": spp, "kernel": sc.irt_kernel_name(int(ids.numel()), spp),
+           "kernel_variant": sc.irt_kernel_variant(int(ids.numel()), spp, "uniform")}
     if probe:
         v = st.cpu().tolist()
         out["probe"] = dict(zip(NAMES, v[8:8 + len(NAMES)]))
@@ -130,7 +131,7 @@ def main():
     t_probe = full["probe"]["kernel_ms"] * 1e-3
     clock = p["chunk_cycles"] / W / t_probe                       # if the probes cover the waves' lifetime this is the shader clock
     att = per_step(p)
-    out = {"workload": a.workload, "kernel": full["shipped"]["kernel"], "kernel_src_sha": bench.kernel_src_sha(), "rays_per_launch": full["shipped"]["rays"],
+    out = {"workload": a.workload, "kernel": full["shipped"]["kernel"], "kernel_variant": full["shipped"].get("kernel_variant"), "kernel_src_sha": bench.kernel_src_sha(), "rays_per_launch": full["shipped"]["rays"],
            "resident_waves": W, "full_occupancy": {"shipped_kernel_ms": round(full["shipped"]["kernel_ms"], 3), "probe_kernel_ms": round(full["probe"]["kernel_ms"], 3),
                                                    "probe_overhead": round(full["probe"]["kernel_ms"] / full["shipped"]["kernel_ms"] - 1.0, 4),
                                                    "implied_clock_ghz": round(clock / 1e9, 3), "raw": p, "per_step": att}}
