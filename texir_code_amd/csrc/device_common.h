@@ -56,11 +56,9 @@ constexpr int kLstk = kLdsStack / 2;                    // the single-ray tracin
 
 // sample_util.py:41  float32(double(i)/double(N)).  For N = 2^k (and i < 2^24) the quotient is exact in float32, so the
 // multiply by the exact reciprocal gives the identical value without a float64 division.
-// POW2: the caller guarantees N = 2^k <= 2^24 (i < N), so only the exact-reciprocal arm is compiled (the same expression: the same bits)
-template <bool POW2 = false>
+// (a caller that knows N = 2^k <= 2^24 at compile time takes the product alone, on its own exact 1 / N: texel_sample_dir<MODE>(i, inv_n, ...))
 __device__ __forceinline__ float ham0(uint32_t i, uint32_t N)
 {
-    if constexpr (POW2) return (float)i * (1.0f / (float)N);
     if ((N & (N - 1u)) == 0u && i < (1u << 24)) return (float)i * (1.0f / (float)N);
     return (float)((double)i / (double)N);
 }
@@ -137,13 +135,20 @@ __device__ __forceinline__ Texel load_texel(const float* __restrict__ pos, const
 }
 
 // direction of sample i of N of a texel with shifts (sh0, sh1) and frame f, as the IrT kernels take it (no roughness: modes 0, 1)
-// (MODE, POW2: the compile-time arms of polar and ham0)
-template <int MODE = -1, bool POW2 = false>
 __device__ __forceinline__ void texel_sample_dir(int mode, uint32_t i, uint32_t N, float sh0, float sh1, const Frame& f, float* d)
 {
-    const float s0 = shift_wrap_clamp(ham0<POW2>(i, N), sh0);
+    const float s0 = shift_wrap_clamp(ham0(i, N), sh0);
     const float s1 = shift_wrap_clamp(ham1(i), sh1);
-    sample_dir<MODE>(mode, s0, s1, 0.f, f, d);
+    sample_dir(mode, s0, s1, 0.f, f, d);
+}
+// ... for N = 2^k <= 2^24 and a compile-time MODE, on the caller's inv_n = 1 / N (exact): ham0's product, the same bits
+template <int MODE>
+__device__ __forceinline__ void texel_sample_dir(uint32_t i, float inv_n, float sh0, float sh1, const Frame& f, float* d)
+{
+    static_assert(MODE == 0 || MODE == 1, "the IrT kernels' modes");
+    const float s0 = shift_wrap_clamp((float)i * inv_n, sh0);
+    const float s1 = shift_wrap_clamp(ham1(i), sh1);
+    sample_dir<MODE>(MODE, s0, s1, 0.f, f, d);
 }
 
 // corner uvs of the triangle in leaf slot `slot`: a = (uv0, uv1), b = (uv2, -, -)
@@ -154,6 +159,18 @@ __device__ __forceinline__ void tri_uvs(const SC& sc, int slot, float4& a, float
     // one 32-byte record per quad record: (q0, q1), (q2, q3); the even slot is triangle (q0, q1, q2), the odd one (q3, q2, q1)  (bvh_build.h)
     const size_t rec = (size_t)(slot >> 1);
     const float4 A = sc.uvs[2 * rec], B = sc.uvs[2 * rec + 1];
+    const bool odd = (slot & 1) != 0;
+    a = odd ? make_float4(B.z, B.w, B.x, B.y) : A;
+    b = odd ? make_float4(A.z, A.w, 0.f, 0.f) : B;
+}
+// ... for irt_group_kernel's fixed form: both halves of the record loaded at once.  Left to the compiler the select by parity becomes a load of the middle
+// 16 bytes, a wait, a branch and two more loads -- one dependent memory round trip more than the data needs.  The empty asm names all eight words, so
+// both 16-byte loads are issued unconditionally in front of one wait; the values selected are the same.  c4 1342.0 -> 1336.6 ms (profiles/r11).
+__device__ __forceinline__ void tri_uvs(const ShadeDev& sc, int slot, float4& a, float4& b)
+{
+    const size_t rec = (size_t)(slot >> 1);
+    float4 A = sc.uvs[2 * rec], B = sc.uvs[2 * rec + 1];
+    asm volatile("" : "+v"(A.x), "+v"(A.y), "+v"(A.z), "+v"(A.w), "+v"(B.x), "+v"(B.y), "+v"(B.z), "+v"(B.w));
     const bool odd = (slot & 1) != 0;
     a = odd ? make_float4(B.z, B.w, B.x, B.y) : A;
     b = odd ? make_float4(A.z, A.w, 0.f, 0.f) : B;

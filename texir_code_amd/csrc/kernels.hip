@@ -113,6 +113,49 @@ struct IrtAny { static constexpr bool fixed = false; static constexpr int mode =
 template <int MODE, bool COSW>
 struct IrtFixed { static constexpr bool fixed = true; static constexpr int mode = MODE; static constexpr bool cosw = COSW; static constexpr int layout = 4; };
 
+// What a pass of the fixed form needs of its texel, parked in private memory for the whole chunk: the kernel is built for 64 VGPRs, so none of this can
+// stay in registers across the traversal loop.  Left to the register allocator it comes back as one 4-byte reload per value, each placed in front of its
+// first use with a wait of its own -- a dozen L2 round trips in a row per pass.  As ONE 64-byte record it comes back as four 16-byte loads under one wait
+// (park_load): c4 1373.1 -> 1342.0 ms (profiles/r11).  n, U, V: the frame; sh0, sh1: the shifts; nx, ny, nz: the RAW normal; dphi, dth: the texel's cell offsets (park_cell_offsets).
+typedef float ParkVec __attribute__((ext_vector_type(4)));
+struct Parked { float n[3], U[3], V[3], sh0, sh1, nx, ny, nz; uint32_t dphi, dth; };
+
+// device_common.h cell_to_pass_m's two per-texel offsets (the same expressions, rounded separately like the sampling code they belong to)
+__device__ __forceinline__ void park_cell_offsets(float sh0, float sh1, int bphi, int bth, uint32_t& dphi, uint32_t& dth)
+{
+#pragma clang fp contract(off)
+    const uint32_t nphi = 1u << bphi, nth = 1u << bth;
+    dphi = (uint32_t)(sh1 * (float)nphi + 0.5f); dth = (uint32_t)(sh0 * (float)nth + 0.5f);
+}
+// cell_to_pass_m on parked offsets
+__device__ __forceinline__ uint32_t cell_to_pass_parked(uint32_t J, uint32_t dphi, uint32_t dth, int bphi, int bth)
+{
+    const uint32_t nphi = 1u << bphi, nth = 1u << bth;
+    const uint32_t Jphi = J & (nphi - 1u), Jth = J >> bphi;
+    const uint32_t phibin = (Jphi + nphi - (dphi & (nphi - 1u))) & (nphi - 1u);
+    const uint32_t th = (Jth + nth - (dth & (nth - 1u))) & (nth - 1u);
+    const uint32_t low = bphi ? (__brev(phibin) >> (32 - bphi)) : 0u;
+    return (th << bphi) | low;
+}
+__device__ __forceinline__ void park_store(ParkVec* rec, const Parked& k)
+{
+    rec[0] = ParkVec{k.n[0], k.n[1], k.n[2], k.sh0};
+    rec[1] = ParkVec{k.U[0], k.U[1], k.U[2], k.sh1};
+    rec[2] = ParkVec{k.V[0], k.V[1], k.V[2], k.nx};
+    rec[3] = ParkVec{k.ny, k.nz, __uint_as_float(k.dphi), __uint_as_float(k.dth)};
+}
+// The record is read through a private-address-space pointer that has passed through an empty asm: the compiler can neither keep the values live across
+// the traversal nor take the record apart into scalars, and the loads stay scratch loads (not `volatile`: that compiles to flat loads with a wait each).
+// The second asm names all sixteen words at once, so the four loads are issued back to back in front of one wait.
+__device__ __forceinline__ Parked park_load(ParkVec* rec)
+{
+    const ParkVec __attribute__((address_space(5)))* p = (const ParkVec __attribute__((address_space(5)))*)rec;
+    asm volatile("" : "+v"(p) : : "memory");
+    ParkVec a = p[0], b = p[1], c = p[2], d = p[3];
+    asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+    return Parked{{a.x, a.y, a.z}, {b.x, b.y, b.z}, {c.x, c.y, c.z}, a.w, b.w, c.w, d.x, d.y, __float_as_uint(d.z), __float_as_uint(d.w)};
+}
+
 // Multi-texel passes: GRP neighbouring texels per wave, all taking the same absolute direction cell in a pass (device_common.h sample_index_m, cell_to_pass_m).
 template <bool STATS, int WIDTH, int LOG2GRP, typename FIX = IrtAny>
 __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev sc, const float* __restrict__ pos, const float* __restrict__ nrm,
@@ -167,6 +210,12 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
         const float nx = nrm[3 * t], ny = nrm[3 * t + 1], nz = nrm[3 * t + 2];
         const float sh0 = shift[2 * t], sh1 = shift[2 * t + 1];
         const Frame f = make_frame(nx, ny, nz);
+        alignas(16) [[maybe_unused]] ParkVec park[FIX::fixed ? 4 : 1];
+        if constexpr (FIX::fixed) {
+            Parked k = {{f.n[0], f.n[1], f.n[2]}, {f.U[0], f.U[1], f.U[2]}, {f.V[0], f.V[1], f.V[2]}, sh0, sh1, nx, ny, nz, 0u, 0u};
+            park_cell_offsets(sh0, sh1, bphi, bth, k.dphi, k.dth);
+            park_store(park, k);
+        }
         float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
         for (int Lc = part * part_cells; Lc < (part + 1) * part_cells; Lc++) {
             const int J = (FIX::fixed || log2N >= 0) ? wedge_cell(Lc, bphi, bth) : Lc;
@@ -178,10 +227,21 @@ __global__ __launch_bounds__(kBlock, kGroupWaves) void irt_group_kernel(SceneDev
 #endif
             if (live) {
                 // (N not a power of two: only the one-sample-per-pass form is launched, in natural sample order)
-                const uint32_t i = (!FIX::fixed && log2N < 0) ? (uint32_t)J : sample_index_m(cell_to_pass_m((uint32_t)J, sh0, sh1, log2N, LOG2M), (uint32_t)sub, log2N, LOG2M);
-                float d[3];
-                texel_sample_dir<FIX::mode, FIX::fixed>(mode, i, (uint32_t)N, sh0, sh1, f, d);
-                const float ndl = cosw ? 1.f : fminf(fmaxf(nx * d[0] + ny * d[1] + nz * d[2], 0.f), 1.f);       // :170, RAW normal (before the trace: one live register instead of three)
+                float d[3], ndl;
+                if constexpr (FIX::fixed) {
+                    // the pass works on the record's copies (the expressions and their order are the generic arm's: the same bits)
+                    const Parked k = park_load(park);
+                    const Frame kf = {{k.n[0], k.n[1], k.n[2]}, {k.U[0], k.U[1], k.U[2]}, {k.V[0], k.V[1], k.V[2]}};
+                    const uint32_t i = sample_index_m(cell_to_pass_parked((uint32_t)J, k.dphi, k.dth, bphi, bth), (uint32_t)sub, log2N, LOG2M);
+                    // 1 / N for N = 2^log2N built from the exponent where it is used (the float ham0 divides out) instead of held across the traversal
+                    texel_sample_dir<FIX::mode>(i, __uint_as_float((uint32_t)(127 - log2N) << 23), k.sh0, k.sh1, kf, d);
+                    ndl = cosw ? 1.f : fminf(fmaxf(k.nx * d[0] + k.ny * d[1] + k.nz * d[2], 0.f), 1.f);         // :170, RAW normal
+                    asm volatile("" : "+v"(ndl));       // computed HERE: left alone it sinks behind the traversal loop and keeps d and the normal live across it
+                } else {
+                    const uint32_t i = log2N < 0 ? (uint32_t)J : sample_index_m(cell_to_pass_m((uint32_t)J, sh0, sh1, log2N, LOG2M), (uint32_t)sub, log2N, LOG2M);
+                    texel_sample_dir(mode, i, (uint32_t)N, sh0, sh1, f, d);
+                    ndl = cosw ? 1.f : fminf(fmaxf(nx * d[0] + ny * d[1] + nz * d[2], 0.f), 1.f);       // :170, RAW normal (before the trace: one live register instead of three)
+                }
 #if TEXIR_CHAIN_PROBE
                 uint32_t tr_c0 = 0, tr_c1 = 0;
                 if (pass_timed) tr_c0 = probe_clock();
