@@ -292,8 +292,8 @@ TEXIR_API int texir_irt_multi(const texir_scene* scene, const float* pos /*dev*/
  * Caller-owned buffers, the caller's stream, no allocation, no synchronisation, no atomics on results: the call records into a hipGraph, and a replay reads
  * whatever bodies and sets hold then.  K outside 0..8 or M outside 1..8 (reported before any null buffer), a null buffer, N < 1, a workspace that is too
  * small and a scene without the 4-wide tree (TEXIR_BVH_WIDTH=2) are errors with a texir_last_error() text.
- * Not computed here: bodies shadowing each other's direct light F[j] or the bounce G, the body's shadow in the specular term of captured light, the body
- * drawn in a view, triangle-mesh occluders. */
+ * Not computed here: bodies shadowing each other's direct light F[j] or the bounce G, the body drawn in a view, triangle-mesh occluders.  (The body's
+ * shadow in the specular term of captured light: texir_spec_shadow.) */
 TEXIR_API int64_t texir_irt_shadow_workspace_bytes(int64_t n_ids, int32_t N, int32_t M);
 TEXIR_API int texir_irt_shadow(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const float* shift /*dev*/,
                        const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode, const float* bodies /*dev [K][16]*/,
@@ -359,8 +359,9 @@ TEXIR_API int texir_irt_shadow(const texir_scene* scene, const float* pos /*dev*
  * M outside 1..8, inst_obj[j] outside 0..Q-1, N < 1 (all reported before any null buffer), a null buffer, a workspace that is too small, the scene or an
  * occluder without the 4-wide tree and an occluder on another device than the scene are errors with a texir_last_error() text.
  * Not computed here: objects shadowing the inserted emitters' F and R (texir_irt_lights_mesh, texir_spec_lights_mesh do that); the bounce G's own rays,
- * which still ignore the objects; objects lit by the lamps; a union with analytic bodies in one call (the two lost terms double-count where they
- * overlap); the object's shadow in the specular term; the object drawn in a view; more than 8 occluders, instances or sets per call. */
+ * which still ignore the objects; objects lit by the lamps; for the DIFFUSE term, a union with analytic bodies in one call (the two lost terms
+ * double-count where they overlap; texir_spec_shadow takes that union for the specular term, and computes the object's shadow in it); the object drawn in
+ * a view; more than 8 occluders, instances or sets per call. */
 TEXIR_API int64_t texir_irt_shadow_mesh_workspace_bytes(int64_t n_ids, int32_t N, int32_t M);
 TEXIR_API int texir_irt_shadow_mesh(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const float* shift /*dev*/,
                        const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode,
@@ -1004,6 +1005,58 @@ TEXIR_API int texir_spec_lights_mesh(const texir_scene* scene, const float* pos 
                        const texir_scene* const* occluders /*host [Q]*/, int32_t Q /*0..8*/, const int32_t* inst_obj /*host [J]*/,
                        const float* inst_world_to_obj /*dev [J][12]*/, int32_t J /*0..8*/, uint32_t flags /*bit 0: prefilter off*/, float* R /*dev [K][P]*/,
                        uint64_t* stats /*dev [2], nullable*/, void* stream);
+
+/* ---- the shadow inserted emitters' BODIES and inserted mesh OBJECTS cast in the SPECULAR term of the captured light, per pixel (csrc/specshadow.hip).
+ * texir_irt_shadow and texir_irt_shadow_mesh take the intercepted light from the DIFFUSE term; a table in front of a window still left the glossy floor
+ * mirroring the window through it.  This call gives that missing term, for bodies and instances in ONE call and as a union.
+ *
+ * THE RULE.  Inputs: normal (raw), rough, points, cam, shift, P, S and clamp_eps exactly as texir_spec_forward takes them; pixel_ids (device, nullable) with
+ * n_ids as texir_spec_lights has them; bodies: Kb in 0..8 records of 16 float32 in DEVICE memory, the layout and validity rule of texir_irt_shadow;
+ * occluders (HOST, Q in 0..8), inst_obj (HOST) and inst_world_to_obj (DEVICE [J][12], J in 0..8) as texir_irt_shadow_mesh takes them; sets: M in 1..8
+ * uint32 masks in DEVICE memory -- bit k (0..7) = body k, bit 8 + j = instance j; body bits at or above Kb, instance bits at or above 8 + J and bits 16..31
+ * are ignored; a mask that is zero after that yields zeros.  flags bit 0: prefilter off.
+ *   SAMPLES AND RAYS  those of spec_kernel<false, 4>, texir_spec_forward's kernel on a 4-wide tree: sample i = 0..S-1 with s0, s1 from ham0 / ham1 and
+ *               shift_wrap_clamp; spec_sample (csrc/spec_sample.h) on the RAW normal and on v = (cam - x) / max(|cam - x|, 1e-4) gives the direction l and the
+ *               weight w_i; the ray (x = points, l), not normalised; the closest hit t_s with the acceptance test slot >= 0 && t > 1e-4; L_i from the scene's
+ *               OWN texture through the hit shader, in any layout.
+ *   BLOCKED     body k meets sample i with t_b < t_s under the BODY INTERSECTION RULE of texir_irt_shadow with d = l, the same float32 operation sequence (the
+ *               quad two-sided, the sphere a solid ball, t_b = 0 from inside).  Instance j blocks sample i under the BLOCKED rule of texir_irt_shadow_mesh:
+ *               its OBJECT-SPACE RAY sequence, then an accepted triangle with 0 < t < t_s.  B_i = the 16-bit mask of both (bodies in bits 0..7, instances in
+ *               bits 8..15).
+ *   RESULT      lost[m][p] = (1/S) sum_i L_i w_i [sample i has an accepted hit AND (sets[m] & B_i) != 0]: overlapping bodies and instances are a union, not
+ *               a sum.  The relit view takes it from the pixel first: max(rgb - lost[m], 0) (texir_code_amd/irtlight.py add_view(lost_spec=)).
+ *   REDUCTION   spec_kernel's.  The lanes-per-pixel rule of the specular launcher (S when S is a power of two <= 64, else 64; TEXIR_SPEC_LPP is honoured);
+ *               lane sl of a pixel takes the samples q * lpp + sl; per lane acc_m[c] += L[c] * w in ascending pass q, a sample that is not blocked adds
+ *               nothing; then the xor butterfly over the pixel's lanes (offsets lpp / 2, ..., 1); then acc / (float)S.
+ *   CONSEQUENCES (the tests hold them)
+ *             - for a pixel and a set under which EVERY sample with an accepted hit is blocked, and every w_i is finite, lost[m] has, bit for bit, the value
+ *               texir_spec_forward writes into rgb with irr = 0, albedo = 0: the same additions in the same order.
+ *             - for a set no sample's ray meets it is exactly +0.
+ *             - with a non-negative texture 0 <= lost[m] <= that specular term, per value.
+ *             - lost of a superset mask is >= lost of a subset per value: the same non-negative terms are added in the same order and rounding is monotone.
+ *             - the result is a pure function of the inputs: list order, duplicates, ids outside [0, P) (nothing is read or written for them), launch
+ *               shape, stream, graph replay and the prefilter change no bit.
+ * ROUNDING BOUND.  The three existing texts hold unchanged: the direction and weight bounds of the specular sample chain (tests/spec_cases.py derives them);
+ * the body bound of texir_irt_shadow with e_i the chain's direction bound; the instance bound of texir_irt_shadow_mesh with the same e_i.
+ * PREFILTER.  texir_irt_shadow_mesh's box test, unchanged.  A lane whose ray meets no body and no padded box traces nothing.
+ *   out [M][P][3] dev: only listed pixels are written, zeros included (Kb = J = 0: zeros).  pixel_ids NULL => all P (n_ids ignored); a non-null list with
+ *   n_ids == 0 writes nothing.
+ *   stats dev u64[3], nullable: [0] += samples whose ray met some body or some instance's padded box (= the scene rays traced; with the prefilter off every
+ *   valid instance counts as met); [1] += occluder queries really issued: a sample a body already blocks asks only the instances that can still add it to
+ *   a set no blocking body is in (the others change no bit of out), so [1] depends on the sets and is at most the sibling call's count; [2] += blocked
+ *   samples with an accepted hit (B_i != 0 among the bodies and the instances asked: a sample counts once, whichever set or none it falls in).  One atomic
+ *   add per wave and counter.
+ * No workspace.  Caller-owned buffers, the caller's stream, no allocation, no synchronisation, no atomics on results: the call records into a hipGraph, and a
+ * replay sees moved bodies, matrices and sets.  Errors, each reported before any null buffer is touched, with a texir_last_error() text: Kb, Q or J outside
+ * 0..8, M outside 1..8, inst_obj[j] outside 0..Q-1, S < 1, a null buffer, the scene or an occluder without the 4-wide tree (TEXIR_BVH_WIDTH=2), an occluder
+ * on another device than the scene.
+ * Not computed: the object or body drawn in the view; objects lit by the lamps; the shadow on the bounce's own rays; a training backward through lost. */
+TEXIR_API int texir_spec_shadow(const texir_scene* scene, const float* normal /*dev [P,3], raw*/, const float* rough /*dev [P]*/, const float* points /*dev [P,3]*/,
+                       const float* cam /*dev [3]*/, const float* shift /*dev [P,2]*/, const int32_t* pixel_ids /*dev, nullable = all P*/, int64_t n_ids, int64_t P,
+                       int32_t S, float clamp_eps, const float* bodies /*dev [Kb][16]*/, int32_t Kb /*0..8*/, const texir_scene* const* occluders /*host [Q]*/,
+                       int32_t Q /*0..8*/, const int32_t* inst_obj /*host [J]*/, const float* inst_world_to_obj /*dev [J][12]*/, int32_t J /*0..8*/,
+                       const uint32_t* sets /*dev [M]*/, int32_t M /*1..8*/, uint32_t flags /*bit 0: prefilter off*/, float* out /*dev [M][P][3]*/,
+                       uint64_t* stats /*dev [3], nullable*/, void* stream);
 
 /* ---- host-side codec loops of the file formats around the path (both take HOST pointers) ----------------------------
  * PNG scanline un-filtering (filters 0-4, PNG spec 9.2) of zlib-inflated IDAT data: raw [H][stride+1] -> out [H][stride]; replaces the

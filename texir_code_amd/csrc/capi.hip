@@ -1139,4 +1139,33 @@ int texir_spec_lights_mesh(const texir_scene* s, const float* pos, const float* 
     return TEXIR_OK;
 }
 
+/* ---- the shadow of inserted bodies and mesh objects in the specular term of captured light, csrc/specshadow.hip (include/texir_hip.h texir_spec_shadow
+ * states the rule).  The counts first, in the text style of texir_irt_shadow / texir_irt_shadow_mesh: a caller that sized its buffers by a bad count may
+ * hold no buffer at all ---- */
+int texir_spec_shadow(const texir_scene* s, const float* normal, const float* rough, const float* points, const float* cam, const float* shift, const int32_t* pixel_ids,
+                      int64_t n_ids, int64_t P, int32_t S, float ceps, const float* bodies, int32_t Kb, const texir_scene* const* occluders, int32_t Q,
+                      const int32_t* inst_obj, const float* inst_world_to_obj, int32_t J, const uint32_t* sets, int32_t M, uint32_t flags, float* out, uint64_t* stats,
+                      void* stream)
+{
+    const char* fn = "texir_spec_shadow";
+    if (Kb < 0 || Kb > 8) return fail(TEXIR_ERR_INVALID, "%s: Kb must be in 0..8, got %d (a call takes at most 8 bodies)", fn, Kb);
+    if (int e = mesh_counts_check(fn, occluders, Q, inst_obj, J)) return e;
+    if (M < 1 || M > 8) return fail(TEXIR_ERR_INVALID, "%s: M must be in 1..8, got %d (call again for further sets: the results are independent)", fn, M);
+    if (S < 1 || S > 65536) return fail(TEXIR_ERR_INVALID, "%s: S must be in 1..65536, got %d", fn, S);
+    if (!(ceps > 0.0f) || !(ceps - ceps == 0.0f)) return fail(TEXIR_ERR_INVALID, "%s: clamp_eps must be finite and > 0 (got %g)", fn, (double)ceps);
+    if (P < 0 || (pixel_ids && n_ids < 0)) return fail(TEXIR_ERR_INVALID, "%s: negative pixel count", fn);
+    if (P >= (1ll << 31)) return fail(TEXIR_ERR_INVALID, "%s: P too large", fn);
+    if (Kb > 0 && !bodies) return fail(TEXIR_ERR_INVALID, "%s: bodies is null", fn);
+    if (!sets) return fail(TEXIR_ERR_INVALID, "%s: sets is null", fn);
+    const int64_t n = pixel_ids ? n_ids : P;
+    if (n == 0) return TEXIR_OK;
+    if (!s || !normal || !rough || !points || !cam || !shift || !out)
+        return fail(TEXIR_ERR_INVALID, "%s: null argument (scene, normal, rough, points, cam, shift and out are required)", fn);
+    MeshOccluders occ = {};
+    if (int e = mesh_handles_check(fn, s, occluders, Q, inst_obj, inst_world_to_obj, J, occ)) return e;
+    HIP_TRY(launch_spec_shadow(dev_of(s), normal, rough, points, cam, shift, pixel_ids, n, P, S, ceps, bodies, Kb, occ, inst_world_to_obj, J, sets, M, !(flags & 1u), out,
+                               (unsigned long long*)stats, (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 }  // extern "C"

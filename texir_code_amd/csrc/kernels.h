@@ -135,6 +135,12 @@ hipError_t launch_spec_lights_mesh(const SceneDev& sc, const float* pos, const f
                                    const int32_t* ids /*nullable: all P*/, int64_t n, int64_t P, const float* lights /*dev [K][16]*/, int K, int S, float t_max,
                                    float ceps, const MeshOccluders& occ, const float* world_to_obj /*dev [J][12]*/, int J, bool prefilter, float* R /*[K][P]*/,
                                    unsigned long long* stats /*nullable*/, hipStream_t st);
+// specshadow.hip: what the bodies of inserted emitters and J inserted mesh instances take from the SPECULAR term of the captured light, per set (bit k = body
+// k, bit 8 + j = instance j) and listed pixel; spec_kernel's samples, lane assignment and reduction; no workspace (4-wide trees)
+hipError_t launch_spec_shadow(const SceneDev& sc, const float* normal, const float* rough, const float* points, const float* cam /*dev [3]*/, const float* shift,
+                              const int32_t* ids /*nullable: all P*/, int64_t n, int64_t P, int S, float ceps, const float* bodies /*dev [Kb][16]*/, int Kb,
+                              const MeshOccluders& occ, const float* world_to_obj /*dev [J][12]*/, int J, const uint32_t* sets /*dev [M]*/, int M, bool prefilter,
+                              float* out /*[M][P][3]*/, unsigned long long* stats /*nullable, [3]*/, hipStream_t st);
 // occlusion.hip: is anything in the way inside (t_near, t_far)?  One any-hit query per ray (Open3D RaycastingScene.test_occlusions)
 hipError_t launch_trace_occluded(const SceneDev& sc, const float* org, const float* dir, int64_t R, float t_near, float t_far, uint8_t* occluded,
                                  unsigned long long* stats /*nullable*/, hipStream_t st);

@@ -10,8 +10,8 @@ radiance as the texture (Scene.irt_multi, K textures in one traced pass): bounce
 The body's shadow.  A lamp is a body too: Scene.irt_shadow gives, per set of bodies, the part `lost` of the captured irradiance E that arrived along rays
 a body of the set now intercepts; add(E, F, colours, lost=) and add_view(..., lost=) take it away, floored at zero, before the new light is added.
 Computed: the direct light of the new emitters, its bounces off the scene's DIFFUSE albedo, and the shadow the emitters' bodies cast on the captured
-DIFFUSE light.  Not computed: bodies shadowing each other's direct light or the bounce, the bodies' shadow in the specular term of captured light, the
-body drawn in a view, and any specular bounce."""
+DIFFUSE light; with Scene.spec_shadow and add_view(lost_spec=) also the shadow bodies and inserted mesh objects cast in the SPECULAR term of the captured
+light, as one union.  Not computed: bodies shadowing each other's direct light or the bounce, the body drawn in a view, and any specular bounce."""
 import json
 
 import numpy as np
@@ -122,7 +122,7 @@ def add(E, F, colours, lost=None):
     return out
 
 
-def add_view(rgb, albedo, F, R, colours, G=None, lost=None, irr=None):
+def add_view(rgb, albedo, F, R, colours, G=None, lost=None, irr=None, lost_spec=None):
     """a view relit by inserted emitters: rgb + sum_k colours[k] * (albedo / pi * F[k] + R[k]).  rgb, albedo [...,3]; F [K,...] the lights' irradiance
     factors at the view's pixels (Scene.irt_lights), R [K,...] their specular response factors (Scene.spec_lights); colours [K] scalars or [K,3] -> [...,3].
     G: the lights' bounce irradiance at the view's pixels (bounce), [K,...,3] per unit colour -- then colours[k] * (albedo / pi * G[k]) is added too, after
@@ -130,11 +130,18 @@ def add_view(rgb, albedo, F, R, colours, G=None, lost=None, irr=None):
     is what it was without the keyword, bit for bit.  lost [...,3]: what the lights' bodies take from the captured irradiance at the view's pixels
     (Scene.irt_shadow), with irr [...,3] the captured irradiance rgb's diffuse term albedo / pi * irr was made of: the diffuse term becomes
     albedo / pi * max(irr - lost, 0), i.e. albedo / pi * (irr - max(irr - lost, 0)) is taken from rgb before anything is added.  Without irr the
-    floor acts on the whole pixel: max(rgb - albedo / pi * lost, 0).  lost=None: the bits of the call without the keyword.  numpy or torch; the terms are added in ascending k"""
+    floor acts on the whole pixel: max(rgb - albedo / pi * lost, 0).  lost=None: the bits of the call without the keyword.  lost_spec [...,3]: what the
+    bodies and the inserted objects take from the SPECULAR term of the captured light at the view's pixels (Scene.spec_shadow): max(rgb - lost_spec, 0) is
+    taken first, before the diffuse correction and before anything is added.  lost_spec=None: the bits of the call without the keyword.  numpy or torch;
+    the terms are added in ascending k"""
     if len(colours) != F.shape[0] or tuple(R.shape) != tuple(F.shape):
         raise ValueError("%d colours, F %r, R %r: one colour per light and R shaped as F" % (len(colours), tuple(F.shape), tuple(R.shape)))
     if tuple(F.shape[1:]) != tuple(rgb.shape[:-1]) or rgb.shape[-1] != 3 or tuple(albedo.shape) != tuple(rgb.shape):
         raise ValueError("rgb %r, albedo %r and F %r do not match ([...,3], [...,3] and [K,...])" % (tuple(rgb.shape), tuple(albedo.shape), tuple(F.shape)))
+    if lost_spec is not None:
+        if tuple(lost_spec.shape) != tuple(rgb.shape):
+            raise ValueError("lost_spec %r must be shaped as rgb %r" % (tuple(lost_spec.shape), tuple(rgb.shape)))
+        rgb = _floor0(rgb - lost_spec)
     out = rgb
     pi = _colour([PI32], rgb)                     # (an array, not a scalar: a torch division by a Python scalar multiplies by its reciprocal)
     if lost is not None:

@@ -86,6 +86,40 @@ def mesh_instances(device, occluders, instances, poses):
     return occluders, handles, Q, inst, w2o, K
 
 
+def spec_shadow_sets(sets, n_bodies, n_instances):
+    """the `sets` of Scene.spec_shadow as uint32 masks (texir_spec_shadow: bit k = body k, bit 8 + j = instance j): None -> one set holding every body and
+    every instance; else a list whose items are an int mask (0 .. 2^32 - 1, used as it is: the library ignores bits that name nothing) or a pair
+    (body indices, instance indices), each index inside its count -- anything else is a ValueError -> list of Python ints"""
+    Kb, J = int(n_bodies), int(n_instances)
+    if sets is None:
+        return [((1 << Kb) - 1) | (((1 << J) - 1) << 8)]
+    masks = []
+    for m, item in enumerate(sets):
+        if isinstance(item, (int, np.integer)) and not isinstance(item, bool):
+            if not 0 <= int(item) < 1 << 32:
+                raise ValueError("set %d: a mask is a uint32, got %r" % (m, item))
+            masks.append(int(item))
+            continue
+        try:
+            if isinstance(item, (str, bytes)) or any(isinstance(part, (str, bytes)) for part in item):
+                raise TypeError
+            body_ids, inst_ids = item
+            body_ids, inst_ids = [int(k) for k in body_ids], [int(j) for j in inst_ids]
+        except (TypeError, ValueError):
+            raise ValueError("set %d must be an int mask or a pair (body indices, instance indices), got %r" % (m, item))
+        v = 0
+        for k in body_ids:
+            if not 0 <= k < Kb:
+                raise ValueError("set %d names body %d: the call has %d bodies" % (m, k, Kb))
+            v |= 1 << k
+        for j in inst_ids:
+            if not 0 <= j < J:
+                raise ValueError("set %d names instance %d: the call has %d instances" % (m, j, J))
+            v |= 1 << (8 + j)
+        masks.append(v)
+    return masks
+
+
 def _dev_f32(t, device):
     if not torch.is_tensor(t):
         t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))
@@ -557,6 +591,54 @@ class Scene:
             _lib.check(getattr(_lib.lib(), call)(self.h, _lib.ptr(pos), _lib.ptr(nrm), _lib.ptr(rough), _lib.ptr(shift), _lib.ptr(cam), _lib.ptr(ids), n_ids, P,
                                                  _lib.ptr(lights) if K else None, K, int(n_samples), float(t_max), float(clamp_eps),
                                                  _lib.ptr(out) if K else None, _lib.ptr(st), _lib.stream_ptr()))
+        return (out, st) if stats else out
+
+    # -- the shadow of inserted bodies and mesh objects in the specular term of captured light (include/texir_hip.h texir_spec_shadow) --
+    def spec_shadow(self, pos, nrm, rough, shift, cam, n_samples, bodies=None, occluders=None, instances=None, poses=None, sets=None, texel_ids=None,
+                    clamp_eps=1e-14, prefilter=True, out=None, stats=False):
+        """what inserted bodies and mesh objects take from the SPECULAR term of the captured light per pixel: pos, nrm [P,3] (pos already offset, nrm raw),
+        rough [P], shift [P,2] (the pixels' specular shift), cam [3] and n_samples as spec_render takes them; bodies [Kb,16] float32 records (irtlight.pack,
+        Kb <= 8; a device tensor is used in place); occluders, instances, poses as irt_shadow_mesh takes them (host object-to-world poses are inverted in
+        float64, a singular one is a ValueError; a device [J,12] world-to-object tensor is used in place); sets: M <= 8 items, each an int mask (bit k = body
+        k, bit 8 + j = instance j) or a pair (body indices, instance indices) -- spec_shadow_sets -- or an int32 device tensor of M masks, used in place;
+        None: one set holding every body and every instance -> lost [M, P, 3]: lost[m] is the part of spec_render's specular term (irr = 0, albedo = 0) that
+        arrived along rays a body or an instance of set m now intercepts, a union, not a sum; the relit pixel is max(rgb - lost[m], 0)
+        (irtlight.add_view(lost_spec=)).  texel_ids: pixel ids, only listed pixels are written.  prefilter=False: every lane asks every instance (the same
+        bits, slower).  stats=True: also int64 [3] = (samples whose ray met a body or a box: the scene rays traced, occluder queries, blocked samples)"""
+        pos = _dev_f32(pos, self.device).reshape(-1, 3)
+        nrm = _dev_f32(nrm, self.device).reshape(-1, 3)
+        P = pos.shape[0]
+        rough = _dev_f32(rough, self.device).reshape(P)
+        shift = _dev_f32(shift, self.device).reshape(P, 2)
+        cam = _dev_f32(cam, self.device).reshape(3)
+        bodies = _dev_f32(np.zeros((0, 16), np.float32) if bodies is None else bodies, self.device)
+        if bodies.ndim != 2 or bodies.shape[1] != 16:
+            raise ValueError("bodies must be [Kb,16], got %r" % (tuple(bodies.shape),))
+        Kb = int(bodies.shape[0])
+        _, handles, Q, inst, w2o, J = mesh_instances(self.device, [] if occluders is None else occluders, instances, poses)
+        if torch.is_tensor(sets):
+            masks = sets.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        else:
+            bits = spec_shadow_sets(sets, Kb, J)
+            masks = torch.tensor([v - (1 << 32) if v >= 1 << 31 else v for v in bits], dtype=torch.int32).reshape(-1).to(self.device)
+        M = int(masks.numel())
+        if out is None:
+            out = torch.zeros((M, P, 3), device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (M, P, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float32 [%d,%d,3] on %s" % (M, P, self.device))
+        ids = None
+        n_ids = 0
+        if texel_ids is not None:
+            ids = texel_ids.to(device=self.device, dtype=torch.int32).contiguous()
+            n_ids = ids.numel()
+        st = torch.zeros(3, device=self.device, dtype=torch.int64) if stats else None
+        empty = P == 0 or (texel_ids is not None and n_ids == 0)           # (an EMPTY id list must not reach the library as "no list = all pixels")
+        if not empty:
+            _lib.check(_lib.lib().texir_spec_shadow(self.h, _lib.ptr(nrm), _lib.ptr(rough), _lib.ptr(pos), _lib.ptr(cam), _lib.ptr(shift), _lib.ptr(ids), n_ids, P,
+                                                    int(n_samples), float(clamp_eps), _lib.ptr(bodies) if Kb else None, Kb,
+                                                    C.cast(handles, C.c_void_p) if Q else None, Q, _lib.ptr(inst) if J else None, _lib.ptr(w2o) if J else None, J,
+                                                    _lib.ptr(masks) if M else None, M, 0 if prefilter else 1, _lib.ptr(out) if M else None, _lib.ptr(st),
+                                                    _lib.stream_ptr()))
         return (out, st) if stats else out
 
 

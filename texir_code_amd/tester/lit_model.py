@@ -7,6 +7,7 @@
     test.light_shadows = false        the shadow the lamps' bodies cast on the captured diffuse light (Scene.irt_shadow), traced once at construction
     test.light_shadow_samples = 256   samples per texel
     test.objects = none               | <irtobject list or json, the form of train.irt_objects>: inserted mesh objects that shadow the lamps' light
+    test.spec_shadows = false         the shadow the lamps' bodies and the objects cast in the SPECULAR term of the captured light (Scene.spec_shadow), per view
 
 With lights, render() adds their diffuse and specular response to every rendered view, sum_k colour_k (albedo / pi F[k] + R[k]) (Scene.irt_lights,
 Scene.spec_lights, irtlight.add_view), at test.light_samples samples per pixel, light and technique, with the pixels' own specular shift and the model's
@@ -18,8 +19,12 @@ private generator, `lost`: what the union of the lamps' bodies takes from the ca
 render() takes albedo / pi * (irr - max(irr - lost, 0)) from the diffuse term before the lamps' light is added (irtlight.add_view(lost=, irr=)).
 With test.objects (it needs test.lights) the objects are loaded once (irtobject.load) and handed to the irt_lights and spec_lights calls of render()
 and to the F that seeds the bounce: the lamps' diffuse and specular light is shadowed by the objects (Scene.irt_lights(occluders=...)).  Not computed with
-objects: the bounce's own rays (they still ignore the objects), the objects lit by the lamps, the objects drawn in the view, their shadow on captured light.
-Not computed: the bodies' shadow in the specular term of captured light, bodies shadowing each other's light, the body drawn in the view, a specular bounce.
+objects: the bounce's own rays (they still ignore the objects), the objects lit by the lamps, the objects drawn in the view, their shadow on captured
+DIFFUSE light.
+With test.spec_shadows (it needs test.lights) render() traces, per view and on the pixels' own replayed specular shift, what the union of the lamps' bodies
+and of the objects takes from the specular term of the captured light (Scene.spec_shadow at the model's own sample count and floor of denominators, one
+set holding all of them) and irtlight.add_view(lost_spec=) takes it from the pixel first, floored at zero.
+Not computed: bodies shadowing each other's light, the body drawn in the view, a specular bounce, the specular shadow on the bounce's own rays.
 With the default `none` the class IS its base: every file Editing, View, Relighting and Error write is unchanged byte for byte.
 This is the class the plugin registry hands the tester runners for models.test_nvdiffrast.MaterialModel."""
 import torch
@@ -82,6 +87,16 @@ def light_shadow_settings(conf):
     return on, int(v)
 
 
+def spec_shadow_setting(conf, lights):
+    """test.spec_shadows (false) -> bool; anything but true / false raises ValueError, and so does true without test.lights (the message names both keys)"""
+    on = conf.get("test.spec_shadows", False)
+    if not isinstance(on, bool):
+        raise ValueError("test.spec_shadows must be true or false, got %r" % (on,))
+    if on and lights is None:
+        raise ValueError("test.spec_shadows needs test.lights = <json of the lights>: the lamps' bodies (and test.objects) cast the shadow")
+    return on
+
+
 class MaterialModel(TM.MaterialModel):
     def __init__(self, conf, *args, **kwargs):
         super().__init__(conf, *args, **kwargs)
@@ -92,6 +107,7 @@ class MaterialModel(TM.MaterialModel):
         self.bounce_tex = None
         self.light_shadows, self.light_shadow_samples = light_shadow_settings(conf)
         self.shadow_tex = None
+        self.spec_shadows = spec_shadow_setting(conf, self.test_lights)
         if self.test_lights is not None and self.light_bounces >= 1:
             self.build_bounce_texture()
         if self.test_lights is not None and self.light_shadows:
@@ -165,9 +181,13 @@ class MaterialModel(TM.MaterialModel):
         F = self.scene.irt_lights(pts, nrm, shift_s, records, n_l, **objects)
         R = self.scene.spec_lights(pts, nrm, roughness.reshape(P), shift_s, cam_position, records, n_l, clamp_eps=TM.TINY_NUMBER, **objects)
         G, lost = getattr(self, "_bounce_irr", None), getattr(self, "_shadow_irr", None)
+        spec = {}                                                            # (off: the calls are the ones they were)
+        if getattr(self, "spec_shadows", False):
+            spec["lost_spec"] = self.scene.spec_shadow(pts, nrm, roughness.reshape(P), shift_s, cam_position, int(self.sample_l[1]), bodies=records,
+                                                       clamp_eps=TM.TINY_NUMBER, **objects)[0]
         if lost is None:
-            res["rgb"] = irtlight.add_view(res["rgb"].reshape(P, 3), alb, F, R, colours, G=None if G is None else G.reshape(P, 3)).reshape(shape + (3,))
+            res["rgb"] = irtlight.add_view(res["rgb"].reshape(P, 3), alb, F, R, colours, G=None if G is None else G.reshape(P, 3), **spec).reshape(shape + (3,))
         else:
             res["rgb"] = irtlight.add_view(res["rgb"].reshape(P, 3), alb, F, R, colours, G=None if G is None else G.reshape(P, 3), lost=lost.reshape(P, 3),
-                                           irr=irr.reshape(P, 3)).reshape(shape + (3,))
+                                           irr=irr.reshape(P, 3), **spec).reshape(shape + (3,))
         return res
