@@ -720,7 +720,7 @@ __global__ __launch_bounds__(256) void grad_add_masked_kernel(float* __restrict_
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t t = i / C;
         const bool on = (mask[t >> 5] >> (t & 31)) & 1u;
-        g[i] = g[i] + (on ? g0[i] : 0.f);
+        if (on) g[i] = g[i] + g0[i];                                 // (a texel whose bit is clear keeps its bits: -0 + 0 would turn a negative zero over)
     }
 }
 
