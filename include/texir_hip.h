@@ -359,9 +359,9 @@ TEXIR_API int texir_irt_shadow(const texir_scene* scene, const float* pos /*dev*
  * M outside 1..8, inst_obj[j] outside 0..Q-1, N < 1 (all reported before any null buffer), a null buffer, a workspace that is too small, the scene or an
  * occluder without the 4-wide tree and an occluder on another device than the scene are errors with a texir_last_error() text.
  * Not computed here: objects shadowing the inserted emitters' F and R (texir_irt_lights_mesh, texir_spec_lights_mesh do that); the bounce G's own rays,
- * which still ignore the objects; objects lit by the lamps; for the DIFFUSE term, a union with analytic bodies in one call (the two lost terms
- * double-count where they overlap; texir_spec_shadow takes that union for the specular term, and computes the object's shadow in it); the object drawn in
- * a view; more than 8 occluders, instances or sets per call. */
+ * which still ignore the objects; for the DIFFUSE term, a union with analytic bodies in one call (the two lost terms
+ * double-count where they overlap; texir_spec_shadow takes that union for the specular term, and computes the object's shadow in it); more than 8
+ * occluders, instances or sets per call. */
 TEXIR_API int64_t texir_irt_shadow_mesh_workspace_bytes(int64_t n_ids, int32_t N, int32_t M);
 TEXIR_API int texir_irt_shadow_mesh(const texir_scene* scene, const float* pos /*dev*/, const float* nrm /*dev*/, const float* shift /*dev*/,
                        const int32_t* texel_ids /*dev, nullable*/, int64_t n_ids, int64_t Nt, int32_t N, int32_t mode,
@@ -993,7 +993,7 @@ TEXIR_API int texir_spec_lights_any(const texir_scene* scene, const float* pos /
  * inst_obj[j] outside 0..Q-1, a null occluder (all reported before any other argument); the scene or an occluder without the 4-wide tree, an occluder on
  * another device than the scene.  K = 0 and an empty list return 0 and write nothing.  Caller-owned buffers, the caller's stream, no allocation, no
  * synchronisation, no workspace: the calls record into a hipGraph; records, camera and matrices are read again on every replay.
- * Not computed: the bounce G's own rays (they still ignore the objects), the objects LIT by the lamps, the object drawn in a view. */
+ * Not computed: the bounce G's own rays (they still ignore the objects).  (The object drawn in a view: texir_gbuffer_cast_mesh.) */
 TEXIR_API int texir_irt_lights_mesh(const texir_scene* scene, const float* pos /*dev [Nt,3]*/, const float* nrm /*dev [Nt,3], raw*/, const float* shift /*dev [Nt,2]*/,
                        const int32_t* texel_ids /*dev, nullable = all Nt*/, int64_t n_ids, int64_t Nt, const float* lights /*dev [K][16]*/, int32_t K /*0..8*/,
                        int32_t S /*1..65536*/, float t_max, const texir_scene* const* occluders /*host [Q]*/, int32_t Q /*0..8*/,
@@ -1050,13 +1050,67 @@ TEXIR_API int texir_spec_lights_mesh(const texir_scene* scene, const float* pos 
  * replay sees moved bodies, matrices and sets.  Errors, each reported before any null buffer is touched, with a texir_last_error() text: Kb, Q or J outside
  * 0..8, M outside 1..8, inst_obj[j] outside 0..Q-1, S < 1, a null buffer, the scene or an occluder without the 4-wide tree (TEXIR_BVH_WIDTH=2), an occluder
  * on another device than the scene.
- * Not computed: the object or body drawn in the view; objects lit by the lamps; the shadow on the bounce's own rays; a training backward through lost. */
+ * Not computed: the body drawn in the view (the object: texir_gbuffer_cast_mesh); the shadow on the bounce's own rays; a training backward through lost. */
 TEXIR_API int texir_spec_shadow(const texir_scene* scene, const float* normal /*dev [P,3], raw*/, const float* rough /*dev [P]*/, const float* points /*dev [P,3]*/,
                        const float* cam /*dev [3]*/, const float* shift /*dev [P,2]*/, const int32_t* pixel_ids /*dev, nullable = all P*/, int64_t n_ids, int64_t P,
                        int32_t S, float clamp_eps, const float* bodies /*dev [Kb][16]*/, int32_t Kb /*0..8*/, const texir_scene* const* occluders /*host [Q]*/,
                        int32_t Q /*0..8*/, const int32_t* inst_obj /*host [J]*/, const float* inst_world_to_obj /*dev [J][12]*/, int32_t J /*0..8*/,
                        const uint32_t* sets /*dev [M]*/, int32_t M /*1..8*/, uint32_t flags /*bit 0: prefilter off*/, float* out /*dev [M][P][3]*/,
                        uint64_t* stats /*dev [3], nullable*/, void* stream);
+
+/* ---- inserted mesh OBJECTS DRAWN IN THE VIEW: the cube G-buffer of texir_gbuffer_cast with up to eight posed mesh instances in it (csrc/gbuffermesh.hip).
+ * The shadow and light passes above shade any point list, points on an object as readily as points of the room; what they lacked is the pass that says, per
+ * pixel, which surface the camera sees -- the room or an instance -- and hands back its world-space position and normal.
+ *
+ * THE RULE.  Inputs: scene, mvp (HOST [6,4,4]), cube_res, flip_v exactly as texir_gbuffer_cast takes them; occluders (HOST, Q in 0..8), inst_obj (HOST) and
+ * inst_world_to_obj (DEVICE [J][12], J in 0..8, read on every launch: a replayed graph sees a moved object) as texir_irt_shadow_mesh takes them; the
+ * occluders' device pointers and boxes enter the kernel arguments by value.  Per pixel of the six faces:
+ *   RAY         eye and direction d are texir_gbuffer_cast's: face_basis in double rounded to float32, the same pixel centre, the same float32 expressions.
+ *   SCENE WALK  first the scene's closest hit, the call gbuffer_kernel<4> makes (trace_closest on the 4-wide tree).  It gives t_best: its t, +inf on a miss.
+ *   INSTANCE WALKS  then the valid instances in index order j = 0 .. J-1 (valid: every word of W[j] is finite): the OBJECT-SPACE RAY (o', d') of
+ *               texir_irt_shadow_mesh with x = eye, its FLOAT32 OPERATION SEQUENCE unchanged; a closest-hit walk of the occluder's tree that STARTS with the far
+ *               bound t_best: a triangle is accepted iff 0 < t < t_best, t the float32 t the leaf test computes (the ray is not normalised, so t along (o', d')
+ *               is t along (eye, d)).  An accepting instance becomes the pixel's surface, its closest accepted t the new t_best.
+ *   TIES        acceptance is strict: the scene wins an exact tie, a lower instance index wins over a higher one.  (A tie is exact between equal RECORDS: the
+ *               same mesh built with other uvs may pair its triangles into other quad records, whose t differs in the last bit.)
+ *   OUTPUTS     a pixel whose surface is the scene, or background: pos, nrm, mask, uv, uv_da, tri_id are bit for bit what texir_gbuffer_cast writes (corner
+ *               normals if set, flip_v, the background constants); inst_id = -1.
+ *               a pixel whose surface is instance j: inst_id = j, mask = 1, tri_id = the row of the occluder's OWN index array + 1, uv = (0, 0) and uv_da = 0
+ *               whatever flip_v is (occluders carry no uvs), and, as a FLOAT32 OPERATION SEQUENCE (each operation separately rounded, no contraction; P0, P1,
+ *               P2 the corners of the stored record, a rotation of the caller's; W = W[j]; rsq = rsqrtf):
+ *                 pos_k = eye_k + t d_k                                                                     (WORLD space)
+ *                 e1 = P1 - P0, e2 = P2 - P0;  n = (e1_y e2_z - e1_z e2_y, e1_z e2_x - e1_x e2_z, e1_x e2_y - e1_y e2_x)
+ *                 n_o = n rsq((n_x n_x + n_y n_y) + n_z n_z)                                                 (the unit geometric normal, the caller's winding)
+ *                 m_c = (W[0][c] n_o,0 + W[1][c] n_o,1) + W[2][c] n_o,2                                      (W^T n_o: W's 3 x 3 part is the inverse of the pose's,
+ *                 nrm_c = m_c rsq((m_0 m_0 + m_1 m_1) + m_2 m_2)                                              so W^T is the pose's inverse transpose)
+ *               The normal is NOT flipped towards the viewer; it is the outward normal of an outward-wound mesh under non-uniform scale and under a mirrored
+ *               pose (negative determinant) alike.
+ *   J = 0, instances no ray meets, and matrices with a non-finite word give texir_gbuffer_cast's bits with inst_id = -1 everywhere.  A singular finite W is
+ *   the caller's error: the outputs of the pixels it touches are unspecified, the call completes.
+ * ROUNDING BOUND (first order, u = 2^-24; eye, the basis and W are exact float32 values, d carries e per component, tests/gbuffer_cases.py bound_arith; the
+ * tests multiply by their factor K).  d' carries texir_irt_shadow_mesh's bound with that e; t carries the closest-hit query's bound_t for it.  Then
+ *               |dpos_k| <= |d_k| bound_t + |t| e_k + u |t d_k| + u |pos_k|
+ *               n_o: the geometric-normal bound e(n_o) of texir_gbuffer_cast (tests/gbuffer_cases.py geometric_normal64);
+ *               e(m_c) = sum_r |W[r][c]| e(n_o,r) + 3 u sum_r |W[r][c] n_o,r|;   q = m . m: e(q) = 2 sum_c |m_c| e(m_c) + 3 u q;
+ *               |dnrm_c| <= e(m_c) / |m| + |m_c| / |m| (e(q) / (2 q) + 5 u)                                  (rsq within 2 ulp = 4 u, the product u)
+ *   The surface is decided unless two surfaces' t differ by less than the sum of their bound_t, or a triangle is within its margin of the ray.
+ * PREFILTER.  A lane walks instance j only if (o', d') passes texir_irt_shadow_mesh's box test, unchanged.  Its argument covers the LEAF TEST -- the 2D origin
+ * inside the sheared triangle and a computed t > 0 -- and the far bound only ever removes accepted triangles (t < t_best on top of t > 0), so the test never
+ * rejects a ray the closest-hit form accepts a triangle for, as it is.  A walk no lane needs is skipped.  flags bit 0 switches the test off (every lane walks
+ * every valid instance): the outputs must not change by a bit, which is how the tests hold this argument.
+ * ONE TRAVERSAL INSTANTIATION: scene and occluders are walked in a wave-uniform loop through the closest-hit form of the traversal, so the kernel owns one LDS
+ * stack, as texir_gbuffer_cast's does.
+ * Outputs, P = 6 c c, all dev: pos, nrm [P,3], mask [P], uv [P,2], uv_da [P,4], tri_id [P], inst_id [P] int32.  Caller-owned buffers, the caller's stream, no
+ * allocation, no synchronisation: the call records into a hipGraph.
+ * ERRORS: TEXIR_ERR_INVALID with a texir_last_error() text, nothing launched and nothing written, for Q or J outside 0..8, inst_obj[j] outside 0..Q-1, a null
+ * occluder handle (all reported before any null buffer), a null argument (inst_id included), cube_res outside 1..16384, a singular or affine mvp, the scene or
+ * an occluder without the 4-wide tree (TEXIR_BVH_WIDTH=2), an occluder on another device than the scene.
+ * Not computed: the lamps' bodies drawn in the view; textured objects (occluders carry no uvs: an object's material is the caller's, per instance); more than
+ * 8 occluders or instances per call. */
+TEXIR_API int texir_gbuffer_cast_mesh(const texir_scene* scene, const float* mvp /*host [6,4,4]*/, int32_t cube_res, int32_t flip_v,
+                       const texir_scene* const* occluders /*host [Q]*/, int32_t Q /*0..8*/, const int32_t* inst_obj /*host [J]*/,
+                       const float* inst_world_to_obj /*dev [J][12]*/, int32_t J /*0..8*/, uint32_t flags /*bit 0: prefilter off*/, float* pos, float* nrm,
+                       float* mask, float* uv, float* uv_da, int32_t* tri_id, int32_t* inst_id /*dev [P]*/, void* stream);
 
 /* ---- host-side codec loops of the file formats around the path (both take HOST pointers) ----------------------------
  * PNG scanline un-filtering (filters 0-4, PNG spec 9.2) of zlib-inflated IDAT data: raw [H][stride+1] -> out [H][stride]; replaces the

@@ -104,6 +104,7 @@ def signatures():
         "texir_irt_lights_mesh": lights[:-3] + mesh + lights[-3:],
         "texir_spec_lights_mesh": spec_lights[:-3] + mesh + spec_lights[-3:],
         "texir_spec_shadow": [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, f32, vp, i32, vp, i32, vp, vp, i32, vp, i32, C.c_uint32, vp, vp, vp],
+        "texir_gbuffer_cast_mesh": [vp, vp, i32, i32] + mesh + [vp, vp, vp, vp, vp, vp, vp, vp],
         "texir_png_unfilter": [vp, i32, i32, i32, vp],
         "texir_hdr_decode_scanlines": (i64, [vp, i64, i32, i32, vp]),
         "texir_rgbe_encode": [vp, i64, vp],

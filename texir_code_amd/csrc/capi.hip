@@ -1168,4 +1168,24 @@ int texir_spec_shadow(const texir_scene* s, const float* normal, const float* ro
     return TEXIR_OK;
 }
 
+/* ---- the cube G-buffer with inserted mesh objects drawn in the view, csrc/gbuffermesh.hip (include/texir_hip.h texir_gbuffer_cast_mesh states the rule).
+ * The conditions on the objects first, as in the sibling passes, then texir_gbuffer_cast's own; nothing is launched or written on an error ---- */
+int texir_gbuffer_cast_mesh(const texir_scene* s, const float* mvp, int32_t c, int32_t flip_v, const texir_scene* const* occluders, int32_t Q, const int32_t* inst_obj,
+                            const float* inst_world_to_obj, int32_t J, uint32_t flags, float* pos, float* nrm, float* mask, float* uv, float* uv_da, int32_t* tri_id,
+                            int32_t* inst_id, void* stream)
+{
+    const char* fn = "texir_gbuffer_cast_mesh";
+    if (int e = mesh_counts_check(fn, occluders, Q, inst_obj, J)) return e;
+    if (!s || !mvp || !pos || !nrm || !mask || !uv || !uv_da || !tri_id || !inst_id)
+        return fail(TEXIR_ERR_INVALID, "%s: null argument (scene, mvp, pos, nrm, mask, uv, uv_da, tri_id and inst_id are required)", fn);
+    if (c <= 0 || c > 16384) return fail(TEXIR_ERR_INVALID, "%s: bad cube_res %d", fn, c);
+    if (!gbuffer_mvp_ok(mvp)) return fail(TEXIR_ERR_INVALID, "%s: an mvp is singular or affine (no eye)", fn);
+    GbufMeshOccluders mo = {};
+    if (int e = mesh_handles_check(fn, s, occluders, Q, inst_obj, inst_world_to_obj, J, mo.occ)) return e;
+    for (int j = 0; j < J; j++) mo.tris[j] = occluders[inst_obj[j]]->dev.tris;
+    HIP_TRY(launch_gbuffer_mesh(dev_of(s), mvp, (const float4*)s->d_cnrm, c, flip_v, mo, inst_world_to_obj, J, !(flags & 1u), pos, nrm, mask, uv, uv_da, tri_id, inst_id,
+                                (hipStream_t)stream));
+    return TEXIR_OK;
+}
+
 }  // extern "C"

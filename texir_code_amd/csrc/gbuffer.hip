@@ -17,13 +17,7 @@ namespace texir {
 // The ray direction is LINEAR in (x,y) (see launch_gbuffer), which gives exact analytic pixel derivatives of the
 // barycentrics -- what nvdiffrast's rast_db / interpolate(diff_attrs='all') provide.
 // ------------------------------------------------------------------------------------------------------------------
-struct FaceBasis { float eye[3], d0[3], dx[3], dy[3]; };   // dir(ndc x, y) = d0 + x*dx + y*dy, from `eye`
-struct GbufArgs {
-    FaceBasis face[6];
-    const float4* cnrm;     // leaf-ordered corner normals, 3 x float4 per triangle (may be null -> geometric normal)
-    int c; int flip_v;
-    float *pos, *nrm, *mask, *uv, *uvda; int32_t* tri;
-};
+// (FaceBasis, GbufArgs: kernels.h -- gbuffermesh.hip casts the same rays)
 
 template <int WIDTH>
 __global__ __launch_bounds__(kBlock) void gbuffer_kernel(SceneDev sc, GbufArgs g)
@@ -108,7 +102,7 @@ static bool invert4(const double* m, double* out)
 //   dir(x,y) = X_h.xyz - eye * X_h.w = x A0 + y A1 + A3,   Ak = rk.xyz - eye * rk.w     (the z term cancels exactly).
 // Evaluated in double on the host: in float32 X_h.w suffers catastrophic cancellation for n = 1e-4, f = 100.
 // One face's basis from its mvp; false where the camera has none: a singular mvp, or an affine one (r2.w == 0: no eye, e.g. an orthographic projection).
-static bool face_basis(const float* mvp16, FaceBasis& fb)
+bool face_basis(const float* mvp16, FaceBasis& fb)
 {
     double m[16], mi[16];
     for (int k = 0; k < 16; k++) m[k] = (double)mvp16[k];

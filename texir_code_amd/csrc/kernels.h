@@ -40,6 +40,15 @@ size_t loss_workspace_bytes(int64_t P, int C, int R);
 hipError_t launch_loss(int stage, int l2, const float* gt, const float* rgb, const float* albedo, const float* rough, const float* rough_womip,
                        const float* empty, const float* gtm, const uint8_t* seg, const uint8_t* hl, const uint8_t* room, int64_t P, int C, int R,
                        int hw, void* workspace, float* out, float* d_rgb, float* d_albedo, float* d_rough, hipStream_t st);
+// gbuffer.hip: the cube G-buffer by primary-ray casting; gbuffermesh.hip: the same rays with inserted mesh instances in the view
+struct FaceBasis { float eye[3], d0[3], dx[3], dy[3]; };   // dir(ndc x, y) = d0 + x*dx + y*dy, from `eye`
+struct GbufArgs {
+    FaceBasis face[6];
+    const float4* cnrm;     // leaf-ordered corner normals, 3 x float4 per triangle (may be null -> geometric normal)
+    int c; int flip_v;
+    float *pos, *nrm, *mask, *uv, *uvda; int32_t* tri;
+};
+bool face_basis(const float* mvp16, FaceBasis& fb);      // one face's basis from its mvp; false where the camera has none (singular or affine)
 bool gbuffer_mvp_ok(const float* mvp_host);      // every face of mvp [6,4,4] has an eye: not singular, not affine
 hipError_t launch_gbuffer(const SceneDev& sc, const float* mvp_host, const float4* cnrm, int c, int flip_v, float* pos, float* nrm, float* mask,
                           float* uv, float* uvda, int32_t* tri, hipStream_t st);
@@ -141,6 +150,15 @@ hipError_t launch_spec_shadow(const SceneDev& sc, const float* normal, const flo
                               const int32_t* ids /*nullable: all P*/, int64_t n, int64_t P, int S, float ceps, const float* bodies /*dev [Kb][16]*/, int Kb,
                               const MeshOccluders& occ, const float* world_to_obj /*dev [J][12]*/, int J, const uint32_t* sets /*dev [M]*/, int M, bool prefilter,
                               float* out /*[M][P][3]*/, unsigned long long* stats /*nullable, [3]*/, hipStream_t st);
+// gbuffermesh.hip: the cube G-buffer with J inserted mesh instances in the view -- per pixel the nearest of the scene and the instances (4-wide trees).
+// The hit shading reads the occluder's triangle records, which MeshOccluders does not carry: the kernel has a struct of its own
+struct GbufMeshOccluders {
+    MeshOccluders occ;
+    const float4* tris[8];       // instance j: the occluder's GpuTri records by leaf-order slot (corners, primitive id)
+};
+hipError_t launch_gbuffer_mesh(const SceneDev& sc, const float* mvp_host, const float4* cnrm, int c, int flip_v, const GbufMeshOccluders& mo,
+                               const float* world_to_obj /*dev [J][12]*/, int J, bool prefilter, float* pos, float* nrm, float* mask, float* uv, float* uvda,
+                               int32_t* tri, int32_t* inst /*[6 c c]*/, hipStream_t st);
 // occlusion.hip: is anything in the way inside (t_near, t_far)?  One any-hit query per ray (Open3D RaycastingScene.test_occlusions)
 hipError_t launch_trace_occluded(const SceneDev& sc, const float* org, const float* dir, int64_t R, float t_near, float t_far, uint8_t* occluded,
                                  unsigned long long* stats /*nullable*/, hipStream_t st);

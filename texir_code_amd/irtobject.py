@@ -9,8 +9,8 @@ is the identity.  At most 8 objects; two entries may name one file (it is loaded
 With the key the IrT stage writes, beside 0_irr_texture.hdr, 0_irr_texture_object<k>_shadow.hdr -- the part of the irradiance that arrived along rays object
 k now intercepts -- and for K > 1 0_irr_texture_objects_shadow.hdr, the same for all objects together (a union, not the sum).  `object-irt` subtracts one of
 them from the base: max(E - lost, 0).  The objects' shadow on the inserted emitters' light F and R is Scene.irt_lights / spec_lights(occluders=...):
-train.irt_light_objects in the stage, test.objects in the evaluation model.  Not computed: the bounce G's own rays (they ignore the objects), the objects lit
-by the lamps, the objects drawn in a view."""
+train.irt_light_objects in the stage, test.objects in the evaluation model.  The objects drawn in a view and lit by the lamps: gbuffer.cast_gbuffer(occluders=...), test.draw_objects
+with test.object_materials (materials() below) in the evaluation model.  Not computed: the bounce G's own rays (they ignore the objects)."""
 import json
 import math
 import os
@@ -90,6 +90,53 @@ def parse(spec, base_dir=None):
             path = os.path.join(base_dir, path)
         out.append((path, pose_matrix(e.get("pose"))))
     return out
+
+
+MATERIALS_KEY = "test.object_materials"
+DEFAULT_ALBEDO, DEFAULT_ROUGHNESS = 0.5, 0.5
+ROUGHNESS_RANGE = (0.01, 0.8)             # the range the trainer clamps a roughness texture to
+
+
+def materials(spec, n_objects):
+    """the value of test.object_materials -> (albedo [K,3], roughness [K]) float32, one row per object of test.objects:
+        none | [ { "albedo": g | [r, g, b], "roughness": r }, ... ] | <path of a json file that holds such a list, bare or under the key "materials">
+    Either key may be missing: albedo 0.5, roughness 0.5.  ValueError names the key: a list of another length than the objects', an albedo that is not
+    finite or negative, a roughness outside [0.01, 0.8]"""
+    K = int(n_objects)
+    albedo, rough = np.full((K, 3), DEFAULT_ALBEDO, np.float32), np.full((K,), DEFAULT_ROUGHNESS, np.float32)
+    if spec is None or (isinstance(spec, str) and spec.strip().lower() == "none"):
+        return albedo, rough
+    if isinstance(spec, str):
+        path = spec
+        if not os.path.exists(path):
+            raise FileNotFoundError("%s = %s: no such file" % (MATERIALS_KEY, path))
+        with open(path) as f:
+            try:
+                spec = json.load(f)
+            except ValueError as e:
+                raise ValueError("%s = %s: not json (%s)" % (MATERIALS_KEY, path, e))
+        if isinstance(spec, dict):
+            spec = spec.get("materials")
+    if not isinstance(spec, (list, tuple)):
+        raise ValueError("%s must be none, a list of {albedo, roughness} or a json file of one, got %r" % (MATERIALS_KEY, spec))
+    if len(spec) != K:
+        raise ValueError("%s has %d entries for %d objects: one entry per object" % (MATERIALS_KEY, len(spec), K))
+    for k, e in enumerate(spec):
+        if not isinstance(e, dict) or set(e) - {"albedo", "roughness"}:
+            raise ValueError("%s: entry %d must be {albedo, roughness}, got %r" % (MATERIALS_KEY, k, e))
+        try:
+            a = np.asarray(e.get("albedo", DEFAULT_ALBEDO), np.float64).reshape(-1)
+            r = float(e.get("roughness", DEFAULT_ROUGHNESS))
+        except (TypeError, ValueError):
+            raise ValueError("%s: entry %d: albedo is a number or [r, g, b], roughness a number, got %r" % (MATERIALS_KEY, k, e))
+        if isinstance(e.get("roughness"), bool) or a.shape not in ((1,), (3,)):
+            raise ValueError("%s: entry %d: albedo is a number or [r, g, b], roughness a number, got %r" % (MATERIALS_KEY, k, e))
+        if not np.isfinite(a).all() or (a < 0).any():
+            raise ValueError("%s: entry %d: albedo must be finite and >= 0, got %r" % (MATERIALS_KEY, k, e.get("albedo")))
+        if not ROUGHNESS_RANGE[0] <= r <= ROUGHNESS_RANGE[1]:
+            raise ValueError("%s: entry %d: roughness must be in [%g, %g], got %r" % ((MATERIALS_KEY, k) + ROUGHNESS_RANGE + (e.get("roughness"),)))
+        albedo[k], rough[k] = a, r
+    return albedo, rough
 
 
 def samples_setting(conf, default_samples):

@@ -19,8 +19,20 @@ private generator, `lost`: what the union of the lamps' bodies takes from the ca
 render() takes albedo / pi * (irr - max(irr - lost, 0)) from the diffuse term before the lamps' light is added (irtlight.add_view(lost=, irr=)).
 With test.objects (it needs test.lights) the objects are loaded once (irtobject.load) and handed to the irt_lights and spec_lights calls of render()
 and to the F that seeds the bounce: the lamps' diffuse and specular light is shadowed by the objects (Scene.irt_lights(occluders=...)).  Not computed with
-objects: the bounce's own rays (they still ignore the objects), the objects lit by the lamps, the objects drawn in the view, their shadow on captured
-DIFFUSE light.
+objects: the bounce's own rays (they still ignore the objects), their shadow on captured DIFFUSE light on the room's pixels.
+    test.draw_objects = false         true (it needs test.objects, and so test.lights): the objects are DRAWN in the view
+    test.object_materials = none      | <list of { "albedo": g | [r, g, b], "roughness": r }, one per object, or a json of one> (irtobject.materials; 0.5, 0.5)
+    test.object_samples = 256         samples per object pixel of its captured irradiance
+With test.draw_objects the view's G-buffer is the instanced one (gbuffer.cast_gbuffer(occluders=...), cached per view): a pixel shows the nearest of the room
+and the objects, forward() also returns inst_id and empty_mask is 1 on object pixels.  On the pixels with inst_id = j >= 0 render() substitutes its inputs
+before it calls the base, after any editing recolouring (a seg fetched at uv 0 cannot repaint an object): albedo and roughness are object j's material, irr
+= max(E - lost, 0) with E = Scene.irt_generate at the pixel and lost = Scene.irt_shadow_mesh over all instances as one set (the captured light the object
+itself and its neighbours intercept), at test.object_samples samples with shifts from a private generator with a fixed seed; the fetched bounce and
+light-shadow terms are 0 there (their uv is not a surface of the atlas).  Everything after that is the code that runs on every pixel: the lamps' F and R use
+the objects as occluders, spec_shadow applies if on, add_view composes -- so the objects are lit and shadowed by the inserted lamps.  Not computed with
+drawn objects: the lamps' bodies drawn in the view; bounce light onto objects; the objects' own shadow on the captured SPECULAR term unless
+test.spec_shadows is on; under relighting=True the base re-traces the diffuse term of every pixel against the room alone, so the objects' own shadow on
+that term is missing there; textured objects (occluders have no uvs).
 With test.spec_shadows (it needs test.lights) render() traces, per view and on the pixels' own replayed specular shift, what the union of the lamps' bodies
 and of the objects takes from the specular term of the captured light (Scene.spec_shadow at the model's own sample count and floor of denominators, one
 set holding all of them) and irtlight.add_view(lost_spec=) takes it from the pixel first, floored at zero.
@@ -34,6 +46,7 @@ from ..texture import texture as tex_fetch
 from . import test_model as TM
 
 BOUNCE_SEED = 20241                       # the private generator of the texel shifts
+OBJECT_SEED = 20242                       # the private generator of the object pixels' irradiance shifts
 
 
 def load_test_lights(spec, device):
@@ -97,6 +110,24 @@ def spec_shadow_setting(conf, lights):
     return on
 
 
+def draw_objects_settings(conf, objects):
+    """test.draw_objects (false), test.object_materials (none) and test.object_samples (256) -> (on, (albedo [K,3], roughness [K]) float32 or None, samples
+    >= 1).  true needs test.objects, and so test.lights: the ValueError names the keys.  Off: the materials are not read"""
+    on = conf.get("test.draw_objects", False)
+    if not isinstance(on, bool):
+        raise ValueError("test.draw_objects must be true or false, got %r" % (on,))
+    if on and objects is None:
+        raise ValueError("test.draw_objects needs test.objects = <list of {obj, pose}> (and so test.lights = <json of the lights>): the objects are what is drawn")
+    v = conf.get("test.object_samples", 256)
+    try:
+        if isinstance(v, bool) or int(v) != float(v) or int(v) < 1:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("test.object_samples must be an integer >= 1, got %r" % (v,))
+    mats = irtobject.materials(conf.get("test.object_materials", "none"), len(objects["instances"])) if on else None
+    return on, mats, int(v)
+
+
 class MaterialModel(TM.MaterialModel):
     def __init__(self, conf, *args, **kwargs):
         super().__init__(conf, *args, **kwargs)
@@ -108,6 +139,9 @@ class MaterialModel(TM.MaterialModel):
         self.light_shadows, self.light_shadow_samples = light_shadow_settings(conf)
         self.shadow_tex = None
         self.spec_shadows = spec_shadow_setting(conf, self.test_lights)
+        self.draw_objects, mats, self.object_samples = draw_objects_settings(conf, self.test_objects)
+        if self.draw_objects:
+            self.object_albedo, self.object_roughness = (torch.from_numpy(m).to(self.device) for m in mats)
         if self.test_lights is not None and self.light_bounces >= 1:
             self.build_bounce_texture()
         if self.test_lights is not None and self.light_shadows:
@@ -146,7 +180,20 @@ class MaterialModel(TM.MaterialModel):
         self.bounce_tex = irtlight.add_indirect(torch.zeros((H, W, 3), device=self.device), G, colours).contiguous()
         return self.bounce_tex
 
+    def _gbuffer(self, mvp, view_id):
+        """with test.draw_objects the instanced G-buffer of the loaded objects (gbuffer.cast_gbuffer(occluders=...)), cached per view as the base's is"""
+        if not getattr(self, "draw_objects", False):
+            return super()._gbuffer(mvp, view_id)
+        key = (str(view_id), hash(mvp.cpu().numpy().tobytes()))
+        gb = self._gb_cache.get(key)
+        if gb is None:
+            gb = GB.cast_gbuffer(self.scene, mvp, self.cube_res, flip_v=True, **self.test_objects)
+            self._gb_cache[key] = gb
+        return gb
+
     def forward(self, mvp, id, cam_position, *args, **kwargs):
+        if getattr(self, "draw_objects", False):
+            return self._forward_drawn(mvp, id, cam_position, *args, **kwargs)
         tex, sh = getattr(self, "bounce_tex", None), getattr(self, "shadow_tex", None)
         if tex is None and sh is None:
             return super().forward(mvp, id, cam_position, *args, **kwargs)
@@ -160,7 +207,51 @@ class MaterialModel(TM.MaterialModel):
         finally:
             self._bounce_irr = self._shadow_irr = None
 
+    def _forward_drawn(self, mvp, id, cam_position, *args, **kwargs):
+        """forward() with test.draw_objects: the base's forward on the instanced G-buffer; render() below learns which pixels show an object from
+        self._inst_id and substitutes their inputs.  The result also has inst_id [6,c,c]; empty_mask is the G-buffer's mask, 1 on object pixels"""
+        gb = self._gbuffer(mvp, id)
+        tex, sh = getattr(self, "bounce_tex", None), getattr(self, "shadow_tex", None)
+        on_obj = (gb["inst_id"] >= 0).unsqueeze(-1)
+        # the fetched bounce and light-shadow terms are zero on object pixels: their uv is not a surface of the atlas
+        if tex is not None:
+            self._bounce_irr = torch.where(on_obj, 0.0, tex_fetch(tex, gb["uv"], gb["uv_da"], "linear-mipmap-linear", self.max_mip_level))
+        if sh is not None:
+            self._shadow_irr = torch.where(on_obj, 0.0, tex_fetch(sh, gb["uv"], gb["uv_da"], "linear-mipmap-linear", self.max_mip_level))
+        self._inst_id = gb["inst_id"]
+        try:
+            res = super().forward(mvp, id, cam_position, *args, **kwargs)
+        finally:
+            self._bounce_irr = self._shadow_irr = self._inst_id = None
+        res["inst_id"] = gb["inst_id"]
+        return res
+
+    def object_inputs(self, inst_id, normal, albedo, roughness, points, irr):
+        """the inputs of render() with the object pixels (inst_id = j >= 0) substituted: albedo and roughness are object j's material; irr = max(E - lost, 0)
+        with E = Scene.irt_generate at the pixel's point and normal and lost = Scene.irt_shadow_mesh over ALL instances as one set -- the captured light the
+        object itself and its neighbours intercept -- both at test.object_samples samples with shifts from a private generator (the CPU generator's stream
+        stays what it is) -> (albedo, roughness, irr), shaped as given"""
+        P = normal.numel() // 3
+        ids = torch.nonzero(inst_id.reshape(P) >= 0)[:, 0]
+        if ids.numel() == 0:
+            return albedo, roughness, irr
+        j = inst_id.reshape(P)[ids].long()
+        alb, rgh, ir = albedo.reshape(P, 3).clone(), roughness.reshape(P).clone(), irr.reshape(P, 3).clone()
+        alb[ids], rgh[ids] = self.object_albedo[j], self.object_roughness[j]
+        gen = torch.Generator().manual_seed(OBJECT_SEED)
+        shift_o = torch.rand(P, 2, generator=gen).to(self.device)
+        pts, nrm = points.reshape(P, 3).contiguous(), normal.reshape(P, 3).contiguous()
+        N = int(self.object_samples)
+        E = self.scene.irt_generate(pts, nrm, shift_o, N, texel_ids=ids.to(torch.int32))
+        J = len(self.test_objects["instances"])
+        lost = self.scene.irt_shadow_mesh(pts, nrm, shift_o, N, sets=[list(range(J))], texel_ids=ids.to(torch.int32), **self.test_objects)[0]
+        ir[ids] = torch.clamp(E[ids] - lost[ids], min=0.0)
+        return alb.reshape(albedo.shape), rgh.reshape(roughness.shape), ir.reshape(irr.shape)
+
     def render(self, normal, albedo, roughness, points, cam_position, irr):
+        inst_id = getattr(self, "_inst_id", None)
+        if inst_id is not None:                                              # (test.draw_objects: after any editing recolouring, before the base)
+            albedo, roughness, irr = self.object_inputs(inst_id, normal, albedo, roughness, points, irr)
         lights = getattr(self, "test_lights", None)
         if lights is None:
             return super().render(normal, albedo, roughness, points, cam_position, irr)
